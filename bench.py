@@ -3,7 +3,7 @@
 AudioToTextCTC(audio_size=64, embed_size=512, vocab_size=29, hidden_size=512)  (SURVEY.md 0.2),
 B = 32 x 1024-frame synthetic log-mel per GPU, CTC targets [32, 100]   (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU; batches shard across ranks (weak scaling, 32 utterances per GPU), one RCCL
@@ -33,6 +33,8 @@ import torch.distributed as dist
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md); measured copy rate ~6300
 PMC_FILE = os.path.join(ROOT, "profiles", "dw_fwd_pmc.json")   # HBM bytes / algorithmic bytes of the depthwise forward kernels (rocprofv3 PMC passes, tools/pmc_table.py --json), tagged with the kernel sources' hash
 B_PER_GPU, T_FRAMES, N_MEL, VOCAB, TEXT_LEN = 32, 1024, 64, 29, 100
+DUMP_MAX_ELEMS = 1 << 17       # --dump-outputs: a larger tensor is written as a fixed, seeded sample of this many of its elements
+DUMP_MAX_BYTES = 64 << 20
 
 
 def dw_source_sha():
@@ -77,6 +79,35 @@ def synth_batch(device, B, seed, frames=T_FRAMES):
     text = torch.randint(1, VOCAB, (B, TEXT_LEN), generator=g)
     text_len = torch.full((B,), TEXT_LEN, dtype=torch.int32)
     return ((audio.to(device), audio_len.to(device)), (text.to(device), text_len.to(device)))
+
+
+def step_outputs(model, loss):
+    """What a caller of the training step holds after it: the loss it returns and, on the model, every parameter's gradient, the
+    updated parameters and the BatchNorm running statistics.  Host fp32 copies, name -> array."""
+    out = {"loss": loss.detach().float().cpu().numpy()}
+    for k, p in model.named_parameters():
+        out["grad." + k] = p.grad.detach().float().cpu().numpy()
+        out["param." + k] = p.detach().float().cpu().numpy()
+    for k, b in model.named_buffers():
+        if b.is_floating_point():
+            out["buffer." + k] = b.detach().float().cpu().numpy()
+    return out
+
+
+def dump_outputs(arrays, path):
+    """Each array as path/<name>.npy, float32.  One with more than DUMP_MAX_ELEMS elements is written as the same sample of its
+    flattened elements in every run (DUMP_MAX_ELEMS sorted indices drawn by numpy's default_rng(1234), which touches no global RNG
+    stream), so the files of two builds compare element for element."""
+    arrays = {k: np.array(v, dtype=np.float32, order="C") for k, v in arrays.items()}
+    for k, a in arrays.items():
+        if a.size > DUMP_MAX_ELEMS:
+            arrays[k] = a.reshape(-1)[np.sort(np.random.default_rng(1234).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def usable_cpus():
@@ -369,7 +400,12 @@ def main():
     ap.add_argument("--diag-stretch-rate", type=int, default=0, help="diagnostic only: every drawn time-stretch uses this rate (percent)")
     ap.add_argument("--no-presize", action="store_true", help="skip the untimed allocator-sizing step at 149 %% length (PMC passes over this "
                     "script want every dispatch of a kernel to be the same problem)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: write what the last of them returned to its "
+                    "caller (loss; every gradient, updated parameter and running statistic of the model) as DIR/<name>.npy, float32, "
+                    "tensors above %d elements as a fixed seeded sample (rank 0)" % DUMP_MAX_ELEMS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from voice100_amd.trainer import TrainStep, init_distributed, launch_ranks
 
@@ -458,6 +494,9 @@ def main():
     if not args.no_kernel_timing:
         kt_main = N.timing_read()
         N.timing_enable(False)
+    # the outputs of the last timed step, taken before any later step of this run overwrites them
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(model, loss), args.dump_outputs)
     # The contract's window above is `value`.  A 20-step window is ~0.07 s, and which of its steps draw a time-stretch moves it
     # by several %: `windows` repeats it (same barrier + synchronise bracket, RNG streams running on) to show the spread.
     windows = []

@@ -39,6 +39,9 @@ class Toy(Voice100ModelBase):
 
 def main():
     outdir = sys.argv[1]
+    if torch.cuda.is_available():
+        # where a GPU is visible init_distributed() would take RCCL and bind one device per rank: this test is gloo on the CPU
+        dist.init_process_group("gloo")
     rank, local_rank, world = init_distributed()
     assert dist.is_initialized() and dist.get_world_size() == world == 2
     torch.manual_seed(100 + rank)                       # deliberately different initial weights per rank

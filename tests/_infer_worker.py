@@ -39,6 +39,9 @@ def make_fn(net):
 def main():
     outdir, n_items = sys.argv[1], int(sys.argv[2])
     subgroup = len(sys.argv) > 3 and sys.argv[3] == "subgroup"
+    if torch.cuda.is_available():
+        # where a GPU is visible init_distributed() would take RCCL and bind one device per rank: this test is gloo on the CPU
+        dist.init_process_group("gloo")
     rank, _, world = init_distributed()
     assert dist.is_initialized() and dist.get_world_size() == world
     g = torch.Generator().manual_seed(11)
