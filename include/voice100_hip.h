@@ -356,6 +356,28 @@ int v100_adam_step(const void* chunks, int nchunks, const void* params, const vo
                    const void* exp_avg_sq, double lr, double beta1, double beta2, double eps, double weight_decay, int step,
                    void* stream);
 
+/* ---- gradient clipping (torch.nn.utils.clip_grad_norm_ / clip_grad_value_; Lightning's gradient_clip_val), on the chunk table and
+ * gradient-pointer table of v100_adam_step.
+ * norm_type: 2 = Euclidean norm, -1 = infinity norm (max |g|, NaN propagated).  clip_mode: 1 = norm, 2 = value.
+ * partials: DEVICE array of doubles, one per chunk: the sum of squares of the chunk's gradient elements (fp32 within a lane, fp64
+ * across lanes) for norm_type 2, max |g| for -1.  A norm that spans several chunk tables (param groups) gives each table its own range
+ * at a fixed offset of one buffer and passes the whole buffer (npartials entries) to the consuming call.
+ * Norm mode (two launches): v100_grad_norm_partials writes partials[0, nchunks); the consuming call (v100_adam_step_clip or v100_grad_clip)
+ * reduces partials[0, npartials) in every workgroup in one fixed order to the total norm -- so every workgroup, launch and run agrees bit
+ * for bit, with no atomics -- forms coef = min(clip / (total + 1e-6), 1) in fp32 (NaN stays NaN) and scales g by it before anything else
+ * reads g; with coef == 1 nothing is written back.  total_norm (DEVICE float, may be NULL) receives the total.
+ * Value mode (one launch): g = clamp(g, -clip, clip); partials, npartials, norm_type and total_norm are not read.
+ * The clipped gradient is written back through `grads` (what p.grad holds after torch's in-place clip).
+ * Return codes: 0 ok; 1 bad nchunks / npartials / norm_type / clip_mode / step; 2 launch error; 3 a required pointer is NULL. */
+int v100_grad_norm_partials(const void* chunks, int nchunks, const void* grads, void* partials, int norm_type, void* stream);
+/* v100_adam_step on the clipped gradient (the weight-decay term is added after the clip, as torch.optim.Adam does after a clip). */
+int v100_adam_step_clip(const void* chunks, int nchunks, const void* params, const void* grads, const void* exp_avg,
+                        const void* exp_avg_sq, double lr, double beta1, double beta2, double eps, double weight_decay, int step,
+                        int clip_mode, double clip, const void* partials, int npartials, int norm_type, void* total_norm, void* stream);
+/* the clip alone, in place: grads scaled by the coefficient (norm) or clamped (value); multi-tensor over the chunk table */
+int v100_grad_clip(const void* chunks, int nchunks, const void* grads, int clip_mode, double clip, const void* partials, int npartials,
+                   int norm_type, void* total_norm, void* stream);
+
 /* ---- K10 log_softmax + CTC (asr.py:148-152: F.log_softmax(-1) then nn.CTCLoss(blank, 'mean', zero_infinity=True)) --
  * logits [B][T][V] fp32, targets [B][Lmax] int64, in_len / tgt_len [B] int32 (device).  Writes nll[b] =
  * -log p(target_b | logits_b) (inf when infeasible) and grad[b][t][c] = d nll_b / d logits[b][t][c] (zero for

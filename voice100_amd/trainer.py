@@ -13,6 +13,7 @@ import torch.distributed as dist
 
 from . import functional as F_
 from .dist import FlatGradBuckets, broadcast_module_state
+from .optim import FusedAdam, clip_grad_norm_, clip_grad_value_
 
 
 def init_distributed(backend: Optional[str] = None):
@@ -80,9 +81,22 @@ class TrainStep:
     With more than one rank the constructor first copies rank 0's parameters and buffers to every rank (DDP's
     construction-time broadcast), so replicas cannot start from different weights.
     precision: the reference recipes' `--trainer.precision` (32 | 16 | "bf16"; None = leave functional.set_matmul_precision as it is).
-    16 -- Lightning's fp16 autocast + GradScaler -- runs as "bf16" (same rate and memory here, no loss scaling needed)."""
+    16 -- Lightning's fp16 autocast + GradScaler -- runs as "bf16" (same rate and memory here, no loss scaling needed).
+    gradient_clip_val / gradient_clip_algorithm: the recipes' `--trainer.gradient_clip_val` / `--trainer.gradient_clip_algorithm`, with
+    Lightning's meanings (None or 0: no clipping; "norm": clip_grad_norm_ over every parameter of the optimizer; "value":
+    clip_grad_value_), applied to the gradient mean over the ranks before the optimizer step.  The norm of the last norm-clipped step
+    is self.last_grad_norm (a 0-dim tensor on the gradients' device)."""
 
-    def __init__(self, model: torch.nn.Module, bucket_bytes: int = 16 << 20, force_exchange: bool = False, precision=None):
+    def __init__(self, model: torch.nn.Module, bucket_bytes: int = 16 << 20, force_exchange: bool = False, precision=None,
+                 gradient_clip_val=None, gradient_clip_algorithm="norm"):
+        algorithm = "norm" if gradient_clip_algorithm is None else str(gradient_clip_algorithm).lower()
+        if algorithm not in ("norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm must be 'norm' or 'value', got {gradient_clip_algorithm!r}")
+        if gradient_clip_val is not None and not float(gradient_clip_val) >= 0:
+            raise ValueError(f"gradient_clip_val must be None or >= 0, got {gradient_clip_val!r}")
+        self.clip_val = float(gradient_clip_val) if gradient_clip_val else None
+        self.clip_algorithm = algorithm
+        self.last_grad_norm = None
         if precision is not None:
             F_.set_matmul_precision(resolve_precision(precision))
         # force_exchange: run the bucketed all-reduce machinery even in a process group of ONE rank (bench.py's
@@ -109,9 +123,29 @@ class TrainStep:
         else:
             loss.backward()
         self.buckets.finish_step()
-        self.optimizer.step()
+        if self.clip_val is None:
+            self.optimizer.step()
+        else:
+            self._clipped_step()
         self.step_idx += 1
         return loss.detach()
+
+    def _clipped_step(self):
+        norm = self.clip_algorithm == "norm"
+        if isinstance(self.optimizer, FusedAdam):                  # clip inside the Adam launch
+            if norm:
+                self.optimizer.step(max_grad_norm=self.clip_val)
+            else:
+                self.optimizer.step(grad_clip_value=self.clip_val)
+            self.last_grad_norm = self.optimizer.last_grad_norm
+            return
+        params = [p for g in self.optimizer.param_groups for p in g["params"]]
+        lib = any(p.grad is not None and p.grad.is_cuda for p in params)
+        if norm:
+            self.last_grad_norm = (clip_grad_norm_ if lib else torch.nn.utils.clip_grad_norm_)(params, self.clip_val)
+        else:
+            (clip_grad_value_ if lib else torch.nn.utils.clip_grad_value_)(params, self.clip_val)
+        self.optimizer.step()
 
     def end_epoch(self):
         if self.scheduler is not None:
