@@ -491,6 +491,34 @@ int v100_world_d4c(const float* x, const int* lengths, const double* f0, int B, 
                    double threshold, int fft_size, const double* randn_table, long long table_len, const double* twiddle,
                    const double* nuttall, int window_length, double* ap, double* coded, float* coded32, void* workspace, void* stream);
 
+/* ---- K15 LSTM recurrence (csrc/lstm.hip) -----------------------------------------------------------------
+ * The recurrent part of nn.LSTM(H, H, bidirectional) over packed, ragged sequences (_asr_v2.py:32-34, the module; :46, its call on a
+ * PackedSequence).  The input projection xproj = x W_ih^T + b_ih and the gradients of W_ih, W_hh and x are v100_pw_gemm / v100_pw_wgrad.
+ * H % 16 == 0, 16 <= H <= 1024; ndir 1 or 2 (one launch runs both directions); 1 <= lens[b] <= T (int32, device).  Gate order i, f, g, o.
+ *   xproj [ndir][B][4H][T], y [B][ndir H][T] (0 at t >= lens[b]), h_n / c_n / dh_n / dc_n [ndir][B][H]; direction 1 runs t = lens[b]-1 .. 0.
+ *   Training (act, cs, hprev all given, or none for inference): act [ndir][T][B][4H] gate activations and cs [ndir][T][B][H] cell states
+ *   by step, hprev [ndir][B][H][T] the h each t read (the X of the dW_hh GEMM).  Backward: dgates [ndir][B][4H][T] = d(pre-activation
+ *   gates), 0 at t >= lens[b]; dh_n / dc_n may be NULL (zero).
+ *   w_prep: W_hh of each direction laid out by v100_lstm_weight_prep (backward = 0 for v100_lstm_fwd, 1 for v100_lstm_bwd), size
+ *   v100_lstm_weight_bytes.  ws: v100_lstm_ws_bytes (backward as above).  sync: v100_lstm_sync_words(B, ndir) 32-bit words, zeroed by
+ *   the call itself; after the call sync[0] != 0 means a hand-off of the persistent form gave up waiting (sync[0] - 1 = the step):
+ *   the outputs are then invalid and the caller raises.
+ *   use_bf16: 0 exact fp32 MFMA, 1 bf16 operands, 2 fp16 operands (inference only); fp32 accumulate and fp32 cell state in every mode.
+ *   persistent: 1 = one launch for all steps when the grid is resident (v100_lstm_persistent_ok), else one launch per step; 0 = one
+ *   launch per step.  Both forms compute bit-identical results. */
+long long v100_lstm_weight_bytes(int H, int ndir, int use_bf16, int backward);
+long long v100_lstm_ws_bytes(int B, int H, int ndir, int backward);
+int v100_lstm_sync_words(int B, int ndir);
+int v100_lstm_persistent_ok(int B, int H, int ndir, int use_bf16, int backward);
+int v100_lstm_weight_prep(const float* w_hh0, const float* w_hh1, int H, int ndir, int use_bf16, int backward, void* out,
+                          void* stream);
+int v100_lstm_fwd(const float* xproj, const void* w_prep, const float* b_hh0, const float* b_hh1, const int* lens, float* y,
+                  float* h_n, float* c_n, float* act, float* cs, float* hprev, void* ws, unsigned* sync, int B, int T, int H,
+                  int ndir, int use_bf16, int persistent, void* stream);
+int v100_lstm_bwd(const float* dy, const float* dh_n, const float* dc_n, const void* w_prep, const int* lens, const float* act,
+                  const float* cs, float* dgates, void* ws, unsigned* sync, int B, int T, int H, int ndir, int use_bf16,
+                  int persistent, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,3 +67,33 @@ def conv_layer_block(blk, x: torch.Tensor, transpose: bool) -> torch.Tensor:
     ln = blk.layer_norm
     x = F.layer_norm(torch.transpose(x, -2, -1), ln.normalized_shape, ln.weight, ln.bias, ln.eps)
     return F.gelu(torch.transpose(x, -2, -1))
+
+
+def lstm(mod, x, lengths=None):
+    """voice100_amd.lstm.LSTM as the aten LSTM op nn.LSTM records (torch.onnx lowers it to ONNX LSTM), on the module's parameters."""
+    from torch.nn.utils.rnn import PackedSequence
+    weights = []
+    for layer in range(mod.num_layers):
+        weights += [w for w in mod.layer_params(layer) if w is not None]
+    ndir = 2 if mod.bidirectional else 1
+    if lengths is not None and not isinstance(x, PackedSequence):
+        # padded input with lengths: the packed round trip, so the padding is 0 and h_n / c_n are each sequence's last step, as eager
+        from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
+        T = x.shape[1] if mod.batch_first else x.shape[0]
+        packed = pack_padded_sequence(x, torch.as_tensor(lengths).cpu(), batch_first=mod.batch_first, enforce_sorted=False)
+        out, hc = lstm(mod, packed)
+        return pad_packed_sequence(out, batch_first=mod.batch_first, total_length=T)[0], hc
+    if isinstance(x, PackedSequence):
+        data, batch_sizes = x.data, x.batch_sizes
+        B = int(batch_sizes[0])
+        z = torch.zeros(mod.num_layers * ndir, B, mod.hidden_size, dtype=data.dtype, device=data.device)
+        out, h, c = torch._VF.lstm(data, batch_sizes, (z, z), weights, mod.bias, mod.num_layers, mod.dropout, mod.training,
+                                   mod.bidirectional)
+        if x.unsorted_indices is not None:
+            h, c = h.index_select(1, x.unsorted_indices), c.index_select(1, x.unsorted_indices)
+        return PackedSequence(out, batch_sizes, x.sorted_indices, x.unsorted_indices), (h, c)
+    B = x.shape[0] if mod.batch_first else x.shape[1]
+    z = torch.zeros(mod.num_layers * ndir, B, mod.hidden_size, dtype=x.dtype, device=x.device)
+    out, h, c = torch._VF.lstm(x, (z, z), weights, mod.bias, mod.num_layers, mod.dropout, mod.training, mod.bidirectional,
+                               mod.batch_first)
+    return out, (h, c)

@@ -17,7 +17,7 @@ from ._base import Voice100ModelBase, tracing
 from .audio import BatchSpectrogramAugumentation
 from .layers import InvertedResidual, PointwiseConv1d
 
-__all__ = ["ConvVoiceEncoder", "LinearCharDecoder", "AudioToTextCTC"]
+__all__ = ["ConvVoiceEncoder", "LinearCharDecoder", "AudioToTextCTC", "AudioToAlignText"]
 
 
 class ConvVoiceEncoder(nn.Module):
@@ -191,3 +191,6 @@ class AudioToTextCTC(Voice100ModelBase):
     def from_argparse_args(args, **kwargs):
         return AudioToTextCTC(embed_size=int(args.embed_size), hidden_size=int(args.hidden_size),
                               learning_rate=args.learning_rate, weight_decay=args.weight_decay, **kwargs)
+
+
+from .asr_v2 import AudioToAlignText  # noqa: E402  (the v2 ASR model, exported beside the v1 one)

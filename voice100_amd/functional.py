@@ -1494,3 +1494,122 @@ def half_length(lengths: torch.Tensor):
 def ctc_loss(logits_btv, targets, input_lengths, target_lengths, blank: int = 0):
     grad_bvt = bool(getattr(logits_btv, "_v100_grad_T", False)) and logits_btv.requires_grad and _CTC_BVT
     return CTCLossFn.apply(logits_btv, targets, input_lengths, target_lengths, blank, grad_bvt)
+
+
+# ---- K15: LSTM layers (nn.LSTM of the v2 models, _asr_v2.py:32-34, 46) ------------------------------------------------------------
+# The persistent form of the recurrence (one launch for all steps) is the default; V100_LSTM_PERSISTENT=0 selects the step form
+# (one launch per step), which computes the same bits and needs no synchronisation between workgroups.
+LSTM_PERSISTENT = os.environ.get("V100_LSTM_PERSISTENT", "1") not in ("", "0")
+
+
+def _lstm_sync(sync: torch.Tensor, layer, what: str) -> None:
+    code = int(sync[0].item())
+    if code:
+        raise RuntimeError(f"lstm layer {layer}: the {what} recurrence gave up waiting for a hand-off at step {code - 1} "
+                           "(the outputs of this call are invalid)")
+
+
+def _lstm_prep(w0, w1, H, ndir, fmt, backward, like):
+    buf = torch.empty(int(N.helper("v100_lstm_weight_bytes", H, ndir, fmt, backward)), dtype=torch.uint8, device=like.device)
+    N.call("v100_lstm_weight_prep", w0.detach(), None if w1 is None else w1.detach(), H, ndir, fmt, backward, buf)
+    return buf
+
+
+def _lstm_scratch(B, H, ndir, backward, like):
+    ws = torch.empty(int(N.helper("v100_lstm_ws_bytes", B, H, ndir, backward)), dtype=torch.uint8, device=like.device)
+    sync = torch.empty(int(N.helper("v100_lstm_sync_words", B, ndir)), dtype=torch.int32, device=like.device)
+    return ws, sync
+
+
+class LSTMLayerFn(torch.autograd.Function):
+    """One layer of nn.LSTM (one or both directions) over padded x [B, C, T] with per-sequence lengths (int32 [B] on the device):
+    y [B, ndir H, T] (0 at t >= len_b, as pad_packed_sequence pads), h_n and c_n [ndir, B, H] at each sequence's own last step.
+    The input projection and every gradient GEMM are K1 launches; the recurrence is csrc/lstm.hip."""
+
+    @staticmethod
+    def forward(ctx, x, lens, precision, persistent, layer, train, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1):
+        _check(x, "lstm")
+        x = x.contiguous()
+        B, C, T = x.shape
+        H = w_hh0.shape[1]
+        ndir = 1 if w_ih1 is None else 2
+        fmt = _fmt(precision)
+        if train:
+            _no_fp16_training(fmt, "lstm")
+        xproj = _f32(ndir, B, 4 * H, T, like=x)
+        for d, (w_ih, b_ih) in enumerate(((w_ih0, b_ih0), (w_ih1, b_ih1))[:ndir]):
+            W = _weights_of(w_ih, 4 * H, C, fmt, False)
+            _pw_gemm(W.w, W.w_bf, x, xproj[d], 4 * H, C, T, B, fmt, bias=None if b_ih is None else b_ih.detach())
+        wp = _lstm_prep(w_hh0, w_hh1, H, ndir, fmt, 0, x)
+        ws, sync = _lstm_scratch(B, H, ndir, 0, x)
+        y = _f32(B, ndir * H, T, like=x)
+        hn = torch.zeros((ndir, B, H), dtype=torch.float32, device=x.device)
+        cn = torch.zeros((ndir, B, H), dtype=torch.float32, device=x.device)
+        act = cs = hprev = None
+        if train:
+            act, cs, hprev = _f32(ndir, T, B, 4 * H, like=x), _f32(ndir, T, B, H, like=x), _f32(ndir, B, H, T, like=x)
+        bh = [None if b is None else b.detach() for b in (b_hh0, b_hh1)]
+        N.call("v100_lstm_fwd", xproj, wp, bh[0], bh[1], lens, y, hn, cn, act, cs, hprev, ws, sync, B, T, H, ndir, fmt,
+               int(bool(persistent)))
+        _lstm_sync(sync, layer, "forward")
+        if train:
+            ctx.save_for_backward(x, lens, act, cs, hprev, w_ih0, w_hh0, w_ih1, w_hh1)
+        ctx.meta = (fmt, bool(persistent), layer, b_ih0 is not None, ndir, H)
+        return y, hn, cn
+
+    @staticmethod
+    def backward(ctx, dy, dhn, dcn):
+        x, lens, act, cs, hprev, w_ih0, w_hh0, w_ih1, w_hh1 = ctx.saved_tensors
+        fmt, persistent, layer, has_bias, ndir, H = ctx.meta
+        B, C, T = x.shape
+        H4 = 4 * H
+        dy = dy.contiguous()
+        dhn = None if dhn is None else dhn.contiguous()
+        dcn = None if dcn is None else dcn.contiguous()
+        wp = _lstm_prep(w_hh0, w_hh1, H, ndir, fmt, 1, x)
+        ws, sync = _lstm_scratch(B, H, ndir, 1, x)
+        dg = _f32(ndir, B, H4, T, like=x)
+        N.call("v100_lstm_bwd", dy, dhn, dcn, wp, lens, act, cs, dg, ws, sync, B, T, H, ndir, fmt, int(persistent))
+        _lstm_sync(sync, layer, "backward")
+        grads = []
+        for d, (w_ih, w_hh) in enumerate(((w_ih0, w_hh0), (w_ih1, w_hh1))[:ndir]):
+            out = []
+            for w, xin, cin in ((w_ih, x, C), (w_hh, hprev[d], H)):
+                S = N.helper("v100_pw_wgrad_splits", B, H4, cin)
+                partial = _f32(S, H4, cin, like=x)
+                dW = _f32(H4, cin, like=x)
+                N.call("v100_pw_wgrad", dg[d], None, None, None, None, 0, xin, None, None, 0, partial, dW, S, B, H4, cin, T, fmt)
+                out.append(dW)
+            db = dbh = None
+            if has_bias:
+                G = N.helper("v100_dw_num_groups", B, H4)
+                part = _f32(G, H4, 2, like=x)
+                N.call("v100_chan_reduce2", dg[d], None, part, G, B, H4, T)
+                db = _f32(H4, like=x)
+                N.call("v100_slab_sum0", part, G, db, H4)
+                dbh = db.clone()
+            grads += [out[0], out[1], db, dbh]
+        if ndir == 1:
+            grads += [None] * 4
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = _f32(B, C, T, like=x)
+            r = None
+            if ndir == 2:
+                W1 = _weights_of(w_ih1, H4, C, fmt, True)
+                r = _f32(B, C, T, like=x)
+                _pw_gemm(W1.wt, W1.wt_bf, dg[1], r, C, H4, T, B, fmt, epi=0)
+            W0 = _weights_of(w_ih0, H4, C, fmt, True)
+            _pw_gemm(W0.wt, W0.wt_bf, dg[0], dx, C, H4, T, B, fmt, r=r, epi=5 if r is not None else 0)
+        return (dx, None, None, None, None, None, *grads)
+
+
+def lstm_layer(x, lens, params, precision: Optional[str] = None, persistent: Optional[bool] = None, layer: int = 0):
+    """x [B, C, T] fp32, lens int32 [B] on the device, params = (w_ih, w_hh, b_ih, b_hh) per direction (biases may be None)
+    -> (y [B, ndir H, T], h_n [ndir, B, H], c_n [ndir, B, H]).
+    The forward saves what backward needs (gate activations, cell states, the h each step read) only when a gradient can be asked
+    for -- autograd on and the input or a parameter requiring one; otherwise it saves nothing, and precision "fp16" is allowed."""
+    p = list(params) + [None] * (8 - len(params))
+    train = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [x] + p)
+    return LSTMLayerFn.apply(x, lens, precision or _PRECISION, LSTM_PERSISTENT if persistent is None else persistent, layer, train,
+                             *p)

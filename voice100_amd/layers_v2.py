@@ -8,8 +8,8 @@ config/tts_en_base.yaml:20-23: 1024->512 k5, ConvTranspose 512->512 k5 s2 p2, 51
 The sub-modules `conv` and `layer_norm` only own the parameters (keys `conv.weight`, `conv.bias`,
 `layer_norm.weight`, `layer_norm.bias` as in the reference); the arithmetic runs on the HIP library:
 dense conv = im2col + K1 MFMA GEMM, ConvTranspose1d = two tap-stacked K1 GEMMs, then one fused
-channel-LayerNorm + GELU kernel.  GPU only, no fallback.  The LSTMs between these blocks stay on
-PyTorch-ROCm (out of scope).
+channel-LayerNorm + GELU kernel.  GPU only, no fallback.  The LSTM between these blocks in the ASR model
+is voice100_amd.lstm.LSTM (K15).
 """
 from typing import List, Tuple
 
