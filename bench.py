@@ -3,7 +3,7 @@
 AudioToTextCTC(audio_size=64, embed_size=512, vocab_size=29, hidden_size=512)  (SURVEY.md 0.2),
 B = 32 x 1024-frame synthetic log-mel per GPU, CTC targets [32, 100]   (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU; batches shard across ranks (weak scaling, 32 utterances per GPU), one RCCL
@@ -12,8 +12,15 @@ gradient all-reduce per step overlapped with backward.  Rank 0 prints ONE JSON l
 A "step" = augmentation + forward + log_softmax/CTC + backward + gradient exchange + Adam, with
 inputs already resident in HBM.  `roofline` = depthwise forward kernel (the north-star's graded
 kernel): algorithmic bytes of its 9 launches per step / their HIP-event time inside the timed
-region.  `cpu_baseline` = the CPU oracle (port of the reference's PyTorch-CPU path) timed on this
-box's host cores on a bounded sample of the same workload.
+region.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the
+headline figures and what the timed steps themselves measured (loss, host enqueue time, launches,
+`roofline`).  Everything that takes runs of its own is behind --full: the extra and sustained
+windows, the host-contention window, the per-family kernel passes and `roofline_step`, the copy
+yardsticks, the fp32 step, the one-rank data-parallel path, the other BASELINE configs and
+`cpu_baseline` (the CPU oracle, a port of the reference's PyTorch-CPU path, timed on the host's
+cores on a bounded sample of the same workload).
 """
 import argparse
 import json
@@ -35,6 +42,9 @@ PMC_FILE = os.path.join(ROOT, "profiles", "dw_fwd_pmc.json")   # HBM bytes / alg
 B_PER_GPU, T_FRAMES, N_MEL, VOCAB, TEXT_LEN = 32, 1024, 64, 29, 100
 DUMP_MAX_ELEMS = 1 << 17       # --dump-outputs: a larger tensor is written as a fixed, seeded sample of this many of its elements
 DUMP_MAX_BYTES = 64 << 20
+# keys of the record that only a --full run measures (a plain run leaves them out)
+FULL_ONLY_KEYS = ("host_under_contention", "windows_ms_per_step", "roofline_step", "kernel_ms_per_step", "kernel_ms_method", "sustained",
+                  "fp32_ms_per_step", "dp_path_single_rank", "launch_graph_diagnostic")
 
 
 def dw_source_sha():
@@ -323,6 +333,83 @@ def other_configs(device, N, F_):
     return out
 
 
+def copy_yardsticks(device, N, sync):
+    """Device-copy rates (GB/s) the depthwise forward's HBM rate is set against: torch's copy_, the library's own copy kernel and a
+    copy with the depthwise kernels' access pattern (None if that one fails)."""
+    src = torch.empty(1 << 28, device=device, dtype=torch.float32).normal_()      # 1 GiB read + 1 GiB write per copy
+    dst = torch.empty_like(src)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    dst.copy_(src); sync()
+    e0.record()
+    for _ in range(10):
+        dst.copy_(src)
+    e1.record(); sync()
+    copy_gbs = 10 * 2 * src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+    # the same 1 GiB -> 1 GiB copy by the library's own 16-byte-per-lane kernel (v100_copy_probe): torch's copy_ is not the
+    # best a kernel can do on this box, so both yardsticks are reported
+    N.call("v100_copy_probe", src, dst, src.numel() * 4); sync()
+    e0.record()
+    for _ in range(10):
+        N.call("v100_copy_probe", src, dst, src.numel() * 4)
+    e1.record(); sync()
+    probe_gbs = 10 * 2 * src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+    del src, dst
+    # ... and a copy with the depthwise kernels' OWN access pattern (v100_rows_copy_probe: 1 KB bf16 rows of a [B][C][T] tensor, one
+    # workgroup per channel, one row per wave at a time, nontemporal) at the wide layers' shape, rotating over 4 buffer sets
+    # (> 256 MB between two uses of a line: HBM, not the Infinity Cache): what this LAYOUT lets a kernel with no arithmetic reach.
+    pat_gbs = None
+    try:
+        sets = [(torch.empty(B_PER_GPU * 2048 * 512 // 2, device=device, dtype=torch.float32).normal_(),
+                 torch.empty(B_PER_GPU * 2048 * 512 // 2, device=device, dtype=torch.float32)) for _ in range(4)]
+        for a_, b_ in sets:
+            N.call("v100_rows_copy_probe", a_, b_, B_PER_GPU, 2048, 1024)
+        sync()
+        e0.record()
+        for i in range(16):
+            a_, b_ = sets[i % 4]
+            N.call("v100_rows_copy_probe", a_, b_, B_PER_GPU, 2048, 1024)
+        e1.record(); sync()
+        pat_gbs = 16 * 2 * B_PER_GPU * 2048 * 1024 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+        del sets
+    except Exception:                                                # noqa: BLE001
+        pat_gbs = None
+    return copy_gbs, probe_gbs, pat_gbs
+
+
+def step_roofline(kt_nom):
+    """Step-level roofline (round-4 review, item 2): algorithmic bytes and 1x1-GEMM flops of ONE nominal step from the shape model
+    (tools/step_model.py: every operand read once, every result written once, in the step's storage formats), the kernel time of a
+    nominal step measured in this run (kt_nom: HIP events in the dispatch packets of every library launch), and the HBM bytes
+    rocprofv3's counters saw for the same step (profiles/step_pmc.json, quoted only for the kernel sources it was measured on)."""
+    try:
+        from tools import step_model
+        fam = step_model.by_family(step_model.step_rows(B_PER_GPU, T_FRAMES))
+        b_alg = sum(f["bytes"] for f in fam.values())
+        fl = sum(f["flops"] for f in fam.values())
+        k_ms = sum(v[1] for v in kt_nom.values()) if kt_nom else None
+        fam_ms = {k: v[1] for k, v in kt_nom.items()}
+        spmc = None
+        sp = os.path.join(ROOT, "profiles", "step_pmc.json")
+        if os.path.exists(sp):
+            spmc = json.load(open(sp))
+            if spmc.get("csrc_sha") != csrc_sha():
+                spmc = None
+        return {"bytes_algorithmic": round(b_alg), "bytes_measured": (spmc or {}).get("bytes_measured_per_step"),
+                "kernel_ms": round(k_ms, 3) if k_ms else None,
+                "achieved_gbs": round(b_alg / (k_ms * 1e-3) / 1e9, 1) if k_ms else None,
+                "frac_of_8TBs": round(b_alg / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if k_ms else None,
+                "hbm_floor_ms": round(b_alg / (HBM_PEAK_GBS * 1e9) * 1e3, 3), "mfma_floor_ms": round(fl / 2.5e15 * 1e3, 3),
+                "gemm_tflops": round(fl / 1e12, 3),
+                "launches": round(sum(v[0] for v in kt_nom.values()), 1) if kt_nom else None,
+                "note": "nominal step (B = 32 x T = 1024, time-stretch off), library launches only; bytes_algorithmic / flops: tools/step_model.py; "
+                        "bytes_measured: rocprofv3 PMC 2*FETCH_SIZE + WRITE_SIZE over every kernel of the step (profiles/step_pmc.json, "
+                        "null when the kernel sources changed since); kernel_ms: HIP events of every launch in this run",
+                "families_ms": {k: round(v, 3) for k, v in fam_ms.items()},
+                "families_algorithmic_mb": {k: round(f["bytes"] / 1e6, 1) for k, f in fam.items()}}
+    except Exception as e:                                           # noqa: BLE001
+        return {"error": f"{type(e).__name__}: {e}"}
+
+
 def lean_line(out):
     """The printed line: same keys and figures, without the long prose / per-launch tables (those are in the details record)."""
     import copy
@@ -385,17 +472,23 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--windows", type=int, default=5, help="extra timed windows of --steps steps after the reported one (spread only)")
-    ap.add_argument("--host-contention", type=int, default=8, help="after the timed region: the same steps beside N-1 busy host processes "
-                    "(what the enqueueing thread of one rank sees when 8 ranks share this host); 0/1 = skip")
-    ap.add_argument("--sustained-seconds", type=float, default=10.0, help="after the contract window: back-to-back steps for at least this "
-                    "long (steady-state clocks; reported as `sustained`, never as `value`); 0 = skip")
-    ap.add_argument("--graph-diag", action="store_true", help="also time a hipGraph replay of the step (timing diagnostic; a failed capture can "
-                    "poison the context, so it is not part of the default run)")
-    ap.add_argument("--no-extras", action="store_true", help="skip fp32_ms_per_step and dp_path_single_rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure everything else this benchmark reports (see the "
+                    "module docstring); the options below marked --full select among those extras")
+    ap.add_argument("--windows", type=int, default=None, help="--full: extra timed windows of --steps steps after the reported one (spread "
+                    "only; default 5)")
+    ap.add_argument("--host-contention", type=int, default=None, help="--full: after the timed region, the same steps beside N-1 busy host "
+                    "processes (what the enqueueing thread of one rank sees when 8 ranks share this host); 0/1 = skip (default 8)")
+    ap.add_argument("--sustained-seconds", type=float, default=None, help="--full: after the contract window, back-to-back steps for at least "
+                    "this long (steady-state clocks; reported as `sustained`, never as `value`); 0 = skip (default 10)")
+    ap.add_argument("--graph-diag", action="store_true", help="--full: also time a hipGraph replay of the step (timing diagnostic; a failed "
+                    "capture can poison the context, so it is not part of a --full run unless asked for)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip fp32_ms_per_step and dp_path_single_rank")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="no HIP-event timing of the depthwise forward inside the timed steps (no "
+                    "`roofline`) and, under --full, no per-family kernel passes")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip other_configs")
+    ap.add_argument("--details", metavar="FILE", default=None, help="also write the full record (every key, before the printed line is "
+                    "shortened) to FILE as JSON (rank 0)")
     ap.add_argument("--diag-no-timestretch", action="store_true", help="diagnostic only (NOT the benchmark workload): never draw a time-stretch")
     ap.add_argument("--diag-stretch-rate", type=int, default=0, help="diagnostic only: every drawn time-stretch uses this rate (percent)")
     ap.add_argument("--no-presize", action="store_true", help="skip the untimed allocator-sizing step at 149 %% length (PMC passes over this "
@@ -406,6 +499,16 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    # the extra windows run only under --full; asking for one in a plain run is an error rather than silently ignored
+    for name, default, off in (("windows", 5, 0), ("host_contention", 8, 1), ("sustained_seconds", 10.0, 0)):
+        v = getattr(args, name)
+        if v is None:
+            setattr(args, name, default if args.full else 0)
+        elif v > off and not args.full:
+            ap.error(f"--{name.replace('_', '-')} {v} measures after the timed steps: it needs --full")
+    if args.graph_diag and not args.full:
+        ap.error("--graph-diag needs --full")
+    full = args.full
 
     from voice100_amd.trainer import TrainStep, init_distributed, launch_ranks
 
@@ -554,6 +657,7 @@ def main():
     kt, kt_all, kt_nom, kt_all_raw = {}, {}, {}, {}
     if not args.no_kernel_timing:
         kt = kt_main
+    if full and not args.no_kernel_timing:
         # per-kernel-family breakdown: a separate pass after the timed region (it slows the step, see above)
         FAM = ["dw_fwd", "dw_bwd_data", "dw_wgrad", "pw_gemm", "pw_wgrad"]
         N.timing_enable(FAM)                                # (round 5: dispatch-packet timestamps for the GEMM families too; r04 and before bracketed them with event markers, ~+0.2 ms)
@@ -581,7 +685,7 @@ def main():
     # same model / optimiser state running on.  Extra key only.
     fp32_line = None
     dp_line = None
-    if world == 1 and not args.no_extras and args.precision == "bf16":
+    if full and world == 1 and not args.no_extras and args.precision == "bf16":
         try:
             F_.set_matmul_precision("fp32")
             for _ in range(2):
@@ -690,44 +794,10 @@ def main():
         elapsed = float(t)
 
     if rank == 0:
-        # the fraction is reported against the nominal HBM rate AND a device-copy rate measured on this box
-        src = torch.empty(1 << 28, device=device, dtype=torch.float32).normal_()      # 1 GiB read + 1 GiB write per copy
-        dst = torch.empty_like(src)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        dst.copy_(src); sync()
-        e0.record()
-        for _ in range(10):
-            dst.copy_(src)
-        e1.record(); sync()
-        copy_gbs = 10 * 2 * src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        # the same 1 GiB -> 1 GiB copy by the library's own 16-byte-per-lane kernel (v100_copy_probe): torch's copy_ is not the
-        # best a kernel can do on this box, so both yardsticks are reported
-        N.call("v100_copy_probe", src, dst, src.numel() * 4); sync()
-        e0.record()
-        for _ in range(10):
-            N.call("v100_copy_probe", src, dst, src.numel() * 4)
-        e1.record(); sync()
-        probe_gbs = 10 * 2 * src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        del src, dst
-        # ... and a copy with the depthwise kernels' OWN access pattern (v100_rows_copy_probe: 1 KB bf16 rows of a [B][C][T] tensor, one
-        # workgroup per channel, one row per wave at a time, nontemporal) at the wide layers' shape, rotating over 4 buffer sets
-        # (> 256 MB between two uses of a line: HBM, not the Infinity Cache): what this LAYOUT lets a kernel with no arithmetic reach.
-        pat_gbs = None
-        try:
-            sets = [(torch.empty(B_PER_GPU * 2048 * 512 // 2, device=device, dtype=torch.float32).normal_(),
-                     torch.empty(B_PER_GPU * 2048 * 512 // 2, device=device, dtype=torch.float32)) for _ in range(4)]
-            for a_, b_ in sets:
-                N.call("v100_rows_copy_probe", a_, b_, B_PER_GPU, 2048, 1024)
-            sync()
-            e0.record()
-            for i in range(16):
-                a_, b_ = sets[i % 4]
-                N.call("v100_rows_copy_probe", a_, b_, B_PER_GPU, 2048, 1024)
-            e1.record(); sync()
-            pat_gbs = 16 * 2 * B_PER_GPU * 2048 * 1024 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-            del sets
-        except Exception:                                            # noqa: BLE001
-            pat_gbs = None
+        # under --full the fraction is also reported against device-copy rates measured on this box
+        copy_gbs = probe_gbs = pat_gbs = None
+        if full:
+            copy_gbs, probe_gbs, pat_gbs = copy_yardsticks(device, N, sync)
         frames = B_PER_GPU * T_FRAMES * world * args.steps
         dw_bytes, _ = encoder_dw_bytes(B_PER_GPU, T_FRAMES)
         roof = None
@@ -748,8 +818,10 @@ def main():
                     "traffic": None, "traffic_source": None, "traffic_per_launch": None,
                     "launches": n, "avg_launch_us": round(ms * 1e3 / n, 2),
                     "algorithmic_bytes_per_launch": round(nbytes / n), "algorithmic_bytes_nominal_step": dw_bytes,
-                    "measured_copy_gbs": round(copy_gbs, 1), "frac_of_measured_copy": round(achieved / copy_gbs, 4),
-                    "copy_probe_gbs": round(probe_gbs, 1), "frac_of_copy_probe": round(achieved / probe_gbs, 4),
+                    "measured_copy_gbs": round(copy_gbs, 1) if copy_gbs else None,
+                    "frac_of_measured_copy": round(achieved / copy_gbs, 4) if copy_gbs else None,
+                    "copy_probe_gbs": round(probe_gbs, 1) if probe_gbs else None,
+                    "frac_of_copy_probe": round(achieved / probe_gbs, 4) if probe_gbs else None,
                     "pattern_copy_gbs": round(pat_gbs, 1) if pat_gbs else None,
                     "frac_of_pattern_copy": round(achieved / pat_gbs, 4) if pat_gbs else None,
                     "note": ("ceiling of this layout: a pure copy with the kernel's own access pattern ([B][C][T] bf16 rows, one workgroup per "
@@ -788,38 +860,7 @@ def main():
                                      "three-tile / general kernels); frac_nominal_step: the nine launches of a 1024-frame step, timed in a separate pass; "
                                      "frac_family: forward + backward depthwise launches together (algorithmic bytes of both / their time) over the seeded "
                                      "sequence, frac_family_nominal_step: on the 1024-frame step")
-        # Step-level roofline (round-4 review, item 2): algorithmic bytes and 1x1-GEMM flops of ONE nominal step from the shape model
-        # (tools/step_model.py: every operand read once, every result written once, in the step's storage formats), the kernel time of a
-        # nominal step measured in THIS run (HIP events in the dispatch packets of every library launch), and the HBM bytes rocprofv3's
-        # counters saw for the same step (profiles/step_pmc.json, quoted only for the kernel sources it was measured on).
-        roof_step = None
-        try:
-            from tools import step_model
-            fam = step_model.by_family(step_model.step_rows(B_PER_GPU, T_FRAMES))
-            b_alg = sum(f["bytes"] for f in fam.values())
-            fl = sum(f["flops"] for f in fam.values())
-            k_ms = sum(v[1] for v in kt_nom.values()) if kt_nom else None
-            fam_ms = {k: v[1] for k, v in kt_nom.items()}
-            spmc = None
-            sp = os.path.join(ROOT, "profiles", "step_pmc.json")
-            if os.path.exists(sp):
-                spmc = json.load(open(sp))
-                if spmc.get("csrc_sha") != csrc_sha():
-                    spmc = None
-            roof_step = {"bytes_algorithmic": round(b_alg), "bytes_measured": (spmc or {}).get("bytes_measured_per_step"),
-                         "kernel_ms": round(k_ms, 3) if k_ms else None,
-                         "achieved_gbs": round(b_alg / (k_ms * 1e-3) / 1e9, 1) if k_ms else None,
-                         "frac_of_8TBs": round(b_alg / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if k_ms else None,
-                         "hbm_floor_ms": round(b_alg / (HBM_PEAK_GBS * 1e9) * 1e3, 3), "mfma_floor_ms": round(fl / 2.5e15 * 1e3, 3),
-                         "gemm_tflops": round(fl / 1e12, 3),
-                         "launches": round(sum(v[0] for v in kt_nom.values()), 1) if kt_nom else None,
-                         "note": "nominal step (B = 32 x T = 1024, time-stretch off), library launches only; bytes_algorithmic / flops: tools/step_model.py; "
-                                 "bytes_measured: rocprofv3 PMC 2*FETCH_SIZE + WRITE_SIZE over every kernel of the step (profiles/step_pmc.json, "
-                                 "null when the kernel sources changed since); kernel_ms: HIP events of every launch in this run",
-                         "families_ms": {k: round(v, 3) for k, v in fam_ms.items()},
-                         "families_algorithmic_mb": {k: round(f["bytes"] / 1e6, 1) for k, f in fam.items()}}
-        except Exception as e:                                       # noqa: BLE001
-            roof_step = {"error": f"{type(e).__name__}: {e}"}
+        roof_step = step_roofline(kt_nom) if full else None
         out = {
             "metric": "audio frames/sec (fwd+bwd) asr_en_base, B=32x1024-frame mel" + (" [DIAGNOSTIC: time-stretch off]" if args.diag_no_timestretch else "") + (f" [DIAGNOSTIC: stretch {args.diag_stretch_rate}% every step]" if args.diag_stretch_rate else ""),
             "value": round(frames / elapsed, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
@@ -856,29 +897,30 @@ def main():
             "dp_path_single_rank": dp_line,
             "launch_graph_diagnostic": graph_diag,
         }
+        if not full:        # a plain run measured none of these
+            for k in FULL_ONLY_KEYS:
+                out.pop(k)
         # the extras must never cost the primary line: any failure in them is reported inside the JSON instead
-        if world == 1 and not args.no_other_configs and args.precision == "bf16":
+        if full and world == 1 and not args.no_other_configs and args.precision == "bf16":
             try:
                 out["other_configs"] = other_configs(device, N, F_)
             except Exception as e:                                   # noqa: BLE001
                 out["other_configs"] = {"error": f"{type(e).__name__}: {e}"}
-        out["cpu_baseline"] = None
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                out["cpu_baseline"] = cpu_baseline()
-            except Exception as e:                                   # noqa: BLE001
-                out["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
+        if full:
+            out["cpu_baseline"] = None
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    out["cpu_baseline"] = cpu_baseline()
+                except Exception as e:                               # noqa: BLE001
+                    out["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
         # ONE line on stdout, kept SHORT (a harness that keeps only a few KB of a run's tail must still see "metric" and "value" at its
         # start): every contract key, the roofline and cpu_baseline objects with their figures, the extras as figures only.  The full
-        # record (per-launch PMC rows, prose provenance of every number, every key of the other configs) goes to stderr and, where the
-        # directory is writable, to gpurun_out/bench_details.json.
+        # record (per-launch PMC rows, prose provenance of every number, every key of the other configs) goes to stderr and, with
+        # --details FILE, to FILE.
         sys.stderr.write("bench details: " + json.dumps(out) + "\n")
-        try:
-            os.makedirs("gpurun_out", exist_ok=True)
-            with open(os.path.join("gpurun_out", "bench_details.json"), "w") as f:
+        if args.details:
+            with open(args.details, "w") as f:
                 json.dump(out, f)
-        except OSError:
-            pass
         json_out.write(json.dumps(lean_line(out)) + "\n")
         json_out.flush()
     if world > 1:

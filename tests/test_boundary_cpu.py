@@ -275,6 +275,33 @@ def test_bench_line_stays_under_3kb():
         assert k in line["cpu_baseline"], k
 
 
+def test_bench_plain_line_keeps_the_headline_keys():
+    """A plain bench.py run leaves out what only --full measures; its printed line still carries every headline key."""
+    import json
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    rec = json.load(open(os.path.join(root, "profiles", "r05_bench_details.json")))
+    for k in bench.FULL_ONLY_KEYS + ("other_configs", "cpu_baseline"):
+        rec.pop(k, None)
+    line = bench.lean_line(rec)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline"):
+        assert k in line, k
+
+
+def test_bench_full_only_options_need_full():
+    """Options that add a measurement after the timed steps are refused without --full (before anything touches a GPU)."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for opt in (["--windows", "2"], ["--sustained-seconds", "3"], ["--host-contention", "4"], ["--graph-diag"]):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + opt, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--full" in r.stderr, (opt, r.returncode, r.stderr[-300:])
+
+
 def test_trainer_precision_values_of_the_reference_recipes():
     """`--trainer.precision` as the reference's README passes it (README.md:189, 212, 233, 284: `16`; Lightning's other spellings):
     16 maps to "bf16" (INTEGRATION.md section 1), anything else Lightning does not know is refused."""

@@ -24,5 +24,5 @@ for rep in 1 2; do
 done
 mkdir -p gpurun_out
 tools/ab_bench_libs.sh build/variants/lib_dws_d1nt0.so build/variants/lib_dws_d1nt1.so
-V100_DW_STREAM=0 V100_DW_STREAM_BWD=0 python bench.py --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "
+V100_DW_STREAM=0 V100_DW_STREAM_BWD=0 python bench.py --full --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.read());print('general', d['ms_per_step'],d['host_enqueue_ms_per_step'],d['windows_ms_per_step'],d['roofline']['frac'],d['roofline']['avg_launch_us'],d['kernel_ms_per_step'])"

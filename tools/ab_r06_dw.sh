@@ -15,7 +15,7 @@ for rep in 1 2; do
 done
 for rep in 1 2; do for v in $STEP; do
   if [ "$v" = base ]; then unset VOICE100_LIB; else export VOICE100_LIB=$PWD/build/variants/lib_$v.so; fi
-  python bench.py --no-cpu-baseline --no-other-configs --no-extras --sustained-seconds 3 --host-contention 0 --windows 2 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-other-configs --no-extras --sustained-seconds 3 --host-contention 0 --windows 2 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.read());r=d['roofline'];print('STEP $v', d['ms_per_step'],'sust',d['sustained']['ms_per_step'],'frac',r['frac'],r.get('frac_nominal_step'),'fam',r.get('frac_family'),r.get('frac_family_nominal_step'),'bwd',r.get('frac_bwd_nominal_step'),'launches',d['launches_per_step'],d['kernel_ms_per_step'],'nominal',d['roofline_step']['families_ms'])"
 done; done
 unset VOICE100_LIB

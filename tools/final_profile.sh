@@ -8,7 +8,7 @@
 tag=${1:-r05}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/final; rm -rf $out; mkdir -p $out
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o p -- python3 bench.py --steps 30 --warmup 5 --windows 0 --host-contention 0 --sustained-seconds 0 --no-extras --no-cpu-baseline --no-other-configs > $out/${tag}_bench_line_under_rocprof.json 2> $out/prof_err.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o p -- python3 bench.py --full --steps 30 --warmup 5 --windows 0 --host-contention 0 --sustained-seconds 0 --no-extras --no-cpu-baseline --no-other-configs > $out/${tag}_bench_line_under_rocprof.json 2> $out/prof_err.txt
 f=$(find $out/prof -name "*kernel_stats.csv" | head -1)
 cp "$f" $out/${tag}_bench_bf16_kernel_stats.csv
 python3 tools/prof_summary.py "$f" 36 60 > $out/${tag}_bench_bf16_summary.txt
@@ -30,9 +30,8 @@ cp $out/dw_fwd_pmc.json profiles/dw_fwd_pmc.json
 rm -rf $out/pmc_dw/*.csv
 python3 tools/gemm_yardstick.py > $out/${tag}_gemm_yardstick.txt 2>> $out/prof_err.txt
 # per-kernel table of a step with EVERY batch stretched to 110 % (T' = 563: the 768-position depthwise forms, five 128-column GEMM tiles)
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o p -- python3 bench.py --steps 20 --warmup 5 --windows 0 --host-contention 0 --sustained-seconds 0 --no-extras --no-cpu-baseline --no-other-configs --diag-stretch-rate 110 > $out/${tag}_stretch110_line_under_rocprof.json 2>> $out/prof_err.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o p -- python3 bench.py --full --steps 20 --warmup 5 --windows 0 --host-contention 0 --sustained-seconds 0 --no-extras --no-cpu-baseline --no-other-configs --diag-stretch-rate 110 > $out/${tag}_stretch110_line_under_rocprof.json 2>> $out/prof_err.txt
 python3 tools/prof_summary.py "$(find $out/prof -name '*kernel_stats.csv' | head -1)" 26 40 > $out/${tag}_stretch110_kernel_summary.txt
 rm -rf $out/prof
-python3 bench.py > $out/${tag}_bench_line.json 2> $out/bench_err.txt
-cp gpurun_out/bench_details.json $out/${tag}_bench_details.json 2>/dev/null
+python3 bench.py --full --details $out/${tag}_bench_details.json > $out/${tag}_bench_line.json 2> $out/bench_err.txt
 tail -c 600 $out/${tag}_bench_line.json
