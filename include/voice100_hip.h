@@ -519,6 +519,44 @@ int v100_lstm_bwd(const float* dy, const float* dh_n, const float* dc_n, const v
                   const float* cs, float* dgates, void* ws, unsigned* sync, int B, int T, int H, int ndir, int use_bf16,
                   int persistent, void* stream);
 
+/* ---- The v2 TTS models (voice100/models/_align_v2.py, _tts_v2.py) -------------------------------------
+ * K16 v2 WORLDLoss, value + gradient in one pass (_layers_v2.py:116-163, with AlignTextToAudio._calc_batch_loss, _tts_v2.py:98-101).
+ * pred [B][Tp][A], A = 2 + S + 2 Cap: hasf0 logit, f0_hat, logspc_hat[S], hascodeap logits[Cap], codeap_hat[Cap] per frame.
+ * RAW targets f0 [B][Tt], logspc [B][Tt][S], codeap [B][Tt][Cap], length [B] int32, and the six WORLDNorm vectors (all required):
+ * hasf0 = f0 >= 30 and hascodeap = codeap < -0.2 are formed on the raw values, then the targets are normalised.  Frames with
+ * t < min(Tp, Tt) and t < length[b] count; loss[5] = (hasf0 BCE, f0 error * hasf0, mean_S logspc error, mean_Cap hascodeap BCE,
+ * mean_Cap codeap error * hascodeap), each summed over those frames and divided by their number.  l1: 0 squared error, 1 absolute.
+ * unit [B][Tp][A] = d loss_term(a) / d pred for unit upstream gradients (0 on frames that do not count).  partial:
+ * v100_world_loss_parts(B, Tp) x 5 floats, added in a fixed order (deterministic, no atomics). */
+int v100_world_loss_v2(const float* pred, const float* f0, const float* logspc, const float* codeap, const int* length,
+                       const float* f0_mean, const float* f0_std, const float* ls_mean, const float* ls_std,
+                       const float* ca_mean, const float* ca_std, float* partial, float* loss, float* unit,
+                       int B, int Tp, int Tt, int S, int Cap, int l1, void* stream);
+/* dpred[b][t][a] = unit[b][t][a] * gout[term(a)], gout [5] on the device */
+int v100_world_loss_v2_bwd(const float* unit, const float* gout, float* dpred, int B, int Tp, int S, int Cap, void* stream);
+/* K17 TextToAlignText's masked L1 loss (_align_v2.py:80-88): pred [B][L][2] fp32, align [B][W] int64 with W >= 2L (the first 2L
+ * entries are the (gap, len) pairs), text_len [B] int32.  loss[0] = sum over rows i < text_len[b] of mean_k |log(align + 1) - pred|
+ * divided by sum_b min(text_len[b], L); unit [B][L][2] = its gradient for a unit upstream gradient.  partial:
+ * v100_align_loss_parts(B, L) floats, added in a fixed order. */
+int v100_align_loss_parts(int B, int L);
+int v100_align_loss(const float* pred, const long long* align, const int* text_len, float* partial, float* loss, float* unit,
+                    int B, int L, int W, void* stream);
+/* dpred = unit * gout[0], gout [1] on the device */
+int v100_align_loss_bwd(const float* unit, const float* gout, float* dpred, int B, int L, void* stream);
+/* TextToAlignText.align, the v2 expansion (_align_v2.py:48-73) batched, with v100_align_expand's two-pass contract: text [B][Lmax]
+ * int64, align [B][Lmax][2] float64 (gap, length), out [B][Tmax] int64 zero padded, out_len [B].  Per utterance over its own
+ * text_len rows: length = head + trunc(sum(align) - align[0][0]) + tail, the sum in fp64 in index order; the running position is
+ * fp64, spans start at max(trunc(t), previous end) and end at max(trunc(t), start + 1), so every token gets at least one frame.
+ * Where the last span's end passes `length` (the reference raises IndexError) the length is that end.  out == NULL: only
+ * out_len is written. */
+int v100_align_expand_v2(const long long* text, const double* align, const int* text_len, long long* out, int* out_len, int B,
+                         int Lmax, int Tmax, int head, int tail, void* stream);
+/* AlignTextToAudio.predict epilogue (_tts_v2.py:80-94): x [B][T][2+S+2Cap] -> f0 = (x0 < 0 ? 0 : x1*std+mean), logspc = x*std+mean,
+ * codeap = (hascodeap logit < 0 ? 0 : x*std+mean), per codeap feature */
+int v100_world_unnormalize_v2(const float* x, float* f0, float* logspc, float* codeap, const float* f0_mean, const float* f0_std,
+                              const float* ls_mean, const float* ls_std, const float* ca_mean, const float* ca_std,
+                              int B, int T, int S, int Cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

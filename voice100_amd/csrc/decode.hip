@@ -187,3 +187,81 @@ extern "C" int v100_align_expand(const long long* text, const double* align, con
                        Tmax, head, tail);
     return v100_launch_status();
 }
+
+// ---- TextToAlignText.align, the v2 expansion (voice100/models/_align_v2.py:48-73), per utterance over its own text_len rows:
+//
+//   length = head + trunc(sum(align) - align[0][0]) + tail
+//   t = head; u = 0
+//   for i: if i > 0: t += gap_i
+//          s = max(trunc(t), u); u = s + 1          trunc = Python int(): toward zero (predict() can give gaps in (-1, 0))
+//          t += len_i
+//          e = max(trunc(t), u); u = e
+//          out[s:e] = text[i]                       every token gets >= 1 frame; head, gaps and tail stay 0
+//
+// t runs in fp64 as the reference's Python floats do.  The sum is fp64 in index order (the reference sums float32 with
+// torch.sum: the two can differ only when sum - align[0][0] lies within rounding of an integer).  The spans are disjoint and
+// increasing, so each output position finds its token by a binary search over the span starts.  Where tiny lengths push the
+// last span's end e past `length` the reference raises IndexError; here the length becomes max(length, e), so every token is
+// written.  One workgroup per utterance; thread 0 walks the serial recurrence (L is a few hundred at most).
+__device__ __forceinline__ int align_trunc(double t) {
+    // int(t), kept inside int: a span past 2^30 frames is not a real utterance
+    return t >= 1073741824.0 ? 1073741824 : (t <= -1073741824.0 ? -1073741824 : (int)t);
+}
+
+__global__ __launch_bounds__(256) void align_expand_v2_kernel(const long long* __restrict__ text, const double* __restrict__ align,
+                                                              const int* __restrict__ text_len, long long* __restrict__ out,
+                                                              int* __restrict__ out_len, int Lmax, int Tmax, int head, int tail) {
+    extern __shared__ int spans[];                 // [2 * Lmax]: s_i, e_i
+    __shared__ int n_sh;
+    const int b = blockIdx.x;
+    const int L = text_len ? max(min(text_len[b], Lmax), 0) : Lmax;
+    const double* al = align + (size_t)b * Lmax * 2;
+    if (threadIdx.x == 0) {
+        double total = 0.0;
+        for (int i = 0; i < L; ++i) { total += al[2 * i]; total += al[2 * i + 1]; }
+        if (L > 0) total -= al[0];
+        long long n = (long long)head + align_trunc(total) + tail;
+        double t = (double)head;
+        int u = 0;
+        for (int i = 0; i < L; ++i) {
+            if (i > 0) t += al[2 * i];
+            const int s = max(align_trunc(t), u);
+            u = s + 1;
+            t += al[2 * i + 1];
+            const int e = max(align_trunc(t), u);
+            u = e;
+            spans[2 * i] = s;
+            spans[2 * i + 1] = e;
+        }
+        if (n < u) n = u;                            // the documented overflow rule (the reference raises IndexError)
+        if (n > 1073741824) n = 1073741824;
+        if (out && n > Tmax) n = Tmax;
+        n_sh = (int)n;
+        out_len[b] = (int)n;
+    }
+    __syncthreads();
+    if (!out) return;                                // length query only
+    const int n = n_sh;
+    long long* o = out + (size_t)b * Tmax;
+    for (int j = threadIdx.x; j < Tmax; j += blockDim.x) {
+        long long v = 0;
+        if (j < n && L > 0 && j >= spans[0]) {
+            int lo = 0, hi = L - 1;                  // the last i with s_i <= j
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (spans[2 * mid] <= j) lo = mid; else hi = mid - 1;
+            }
+            if (j < spans[2 * lo + 1]) v = text[(size_t)b * Lmax + lo];
+        }
+        o[j] = v;
+    }
+}
+
+extern "C" int v100_align_expand_v2(const long long* text, const double* align, const int* text_len, long long* out, int* out_len, int B,
+                                    int Lmax, int Tmax, int head, int tail, void* stream) {
+    if (!text || !align || !out_len) return V100_ERR_NULL;            // out == NULL: only the lengths are written (the caller sizes `out` from them)
+    if (B <= 0 || Lmax <= 0 || Lmax > 8192 || (out && Tmax <= 0) || head < 0 || tail < 0) return V100_ERR_SHAPE;
+    V100_GGL(align_expand_v2_kernel, dim3(B), dim3(256), 2 * Lmax * sizeof(int), (hipStream_t)stream, text, align, text_len, out, out_len,
+                       Lmax, Tmax, head, tail);
+    return v100_launch_status();
+}

@@ -102,6 +102,35 @@ __global__ __launch_bounds__(256) void world_unnormalize_kernel(const float* __r
     }
 }
 
+// AlignTextToAudio.predict's epilogue (_tts_v2.py:80-94): x [B][T][A], A = 2 + S + 2 Cap (hasf0 logit, f0, logspc[S],
+// hascodeap logits[Cap], codeap[Cap]) -> f0 [B][T] zero where the hasf0 logit < 0, logspc [B][T][S], codeap [B][T][Cap] zero
+// where its hascodeap logit < 0; the kept values are x * std + mean.
+__global__ __launch_bounds__(256) void world_unnormalize_v2_kernel(const float* __restrict__ x, float* __restrict__ f0, float* __restrict__ logspc,
+                                                                   float* __restrict__ codeap, const float* __restrict__ f0_mean,
+                                                                   const float* __restrict__ f0_std, const float* __restrict__ ls_mean,
+                                                                   const float* __restrict__ ls_std, const float* __restrict__ ca_mean,
+                                                                   const float* __restrict__ ca_std, int S, int Cap, long rows) {
+    const int A = 2 + S + 2 * Cap;
+    const long total = rows * A;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int a = (int)(i % A);
+        const long r = i / A;
+        if (a == 0 || (a >= 2 + S && a < 2 + S + Cap)) continue;        // the gate logits are read by their gated feature
+        const float v = x[i];
+        if (a == 1) {
+            const float y = fmaf(f0_std[0], v, f0_mean[0]);
+            f0[r] = x[r * A] < 0.f ? 0.f : y;
+        } else if (a < 2 + S) {
+            const int s = a - 2;
+            logspc[r * S + s] = fmaf(ls_std[s], v, ls_mean[s]);
+        } else {
+            const int s = a - 2 - S - Cap;
+            const float y = fmaf(ca_std[s], v, ca_mean[s]);
+            codeap[r * Cap + s] = x[r * A + 2 + S + s] < 0.f ? 0.f : y;
+        }
+    }
+}
+
 __global__ void exp_clip_kernel(const float* __restrict__ x, float* __restrict__ y, float offset, long n) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
         y[i] = fmaxf(expf(x[i]) - offset, 0.f);
@@ -165,5 +194,16 @@ extern "C" int v100_exp_clip(const float* x, float* y, float offset, long long n
     if (!x || !y) return V100_ERR_NULL;
     if (n <= 0) return V100_ERR_SHAPE;
     V100_GGL(exp_clip_kernel, dim3(grid_for((long)n)), dim3(256), 0, (hipStream_t)stream, x, y, offset, (long)n);
+    return v100_launch_status();
+}
+
+extern "C" int v100_world_unnormalize_v2(const float* x, float* f0, float* logspc, float* codeap, const float* f0_mean, const float* f0_std,
+                                         const float* ls_mean, const float* ls_std, const float* ca_mean, const float* ca_std,
+                                         int B, int T, int S, int Cap, void* stream) {
+    if (!x || !f0 || !logspc || !codeap || !f0_mean || !f0_std || !ls_mean || !ls_std || !ca_mean || !ca_std) return V100_ERR_NULL;
+    if (B <= 0 || T <= 0 || S <= 0 || Cap <= 0) return V100_ERR_SHAPE;
+    const long rows = (long)B * T;
+    V100_GGL(world_unnormalize_v2_kernel, dim3(grid_for(rows * (2 + S + 2 * Cap))), dim3(256), 0, (hipStream_t)stream, x, f0, logspc,
+                       codeap, f0_mean, f0_std, ls_mean, ls_std, ca_mean, ca_std, S, Cap, rows);
     return v100_launch_status();
 }

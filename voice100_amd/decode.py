@@ -1,6 +1,7 @@
 """Integer decode / alignment steps on the GPU, bit-exact with the reference:
 greedy CTC decoding (argmax + merge_repeated, voice100/text.py:99-104), ctc_best_path forced alignment
-(voice100/models/align.py:18-66) and TextToAlignTextModel.align (voice100/models/tts.py:89-110)."""
+(voice100/models/align.py:18-66), TextToAlignTextModel.align (voice100/models/tts.py:89-110) and the v2
+TextToAlignText.align (voice100/models/_align_v2.py:48-73)."""
 import torch
 
 from . import _native as N
@@ -53,4 +54,25 @@ def align_expand(text: torch.Tensor, align: torch.Tensor, text_len=None, head: i
     tmax = max(int(out_len.max()), 1)
     out = torch.empty((B, tmax), dtype=torch.int64, device=text.device)
     N.call("v100_align_expand", text, al, tl, out, out_len, B, L, tmax, int(head), int(tail))
+    return out, out_len
+
+
+def align_expand_v2(text: torch.Tensor, align: torch.Tensor, text_len=None, head: int = 5, tail: int = 5):
+    """TextToAlignText.align (_align_v2.py:48-73) batched: text [B, L] int64, align [B, L, 2] (gap, length) ->
+    (aligntext [B, Tmax] int64 zero-padded, lens [B] int32), Tmax = max(lens) (pad_sequence semantics).  See v100_align_expand_v2
+    for the integer rules and the one departure (a last span past the length lengthens the row instead of raising)."""
+    if not text.is_cuda:
+        raise RuntimeError("align_expand_v2: GPU tensors only")
+    text = text.to(torch.int64).contiguous()
+    al = align.to(device=text.device, dtype=torch.float64).contiguous()
+    B, L = text.shape
+    if al.shape != (B, L, 2):
+        raise RuntimeError(f"align_expand_v2: align must be [{B}, {L}, 2], got {list(al.shape)}")
+    tl = text_len.to(device=text.device, dtype=torch.int32).contiguous() if text_len is not None else None
+    out_len = torch.empty((B,), dtype=torch.int32, device=text.device)
+    # pass 1: the lengths only (ONE read-back sizes the output), pass 2: the expansion, exactly that wide
+    N.call("v100_align_expand_v2", text, al, tl, None, out_len, B, L, 0, int(head), int(tail))
+    tmax = max(int(out_len.max()), 1)
+    out = torch.empty((B, tmax), dtype=torch.int64, device=text.device)
+    N.call("v100_align_expand_v2", text, al, tl, out, out_len, B, L, tmax, int(head), int(tail))
     return out, out_len

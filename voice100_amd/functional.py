@@ -1407,6 +1407,109 @@ def world_loss(pred_bta, length, hasf0, f0, logspc, codeap, norm=None, weights=N
     return WorldLossFn.apply(pred_bta, length, hasf0, f0, logspc, codeap, norm, weights, loss == "l1")
 
 
+def world_unnormalize_gate_v2(x_bta, f0_mean, f0_std, ls_mean, ls_std, ca_mean, ca_std):
+    """x [B,T,2+S+2Cap] -> (f0 [B,T], logspc [B,T,S], codeap [B,T,Cap]), f0 and codeap gated by their logits (_tts_v2.py:80-94)."""
+    if x_bta.is_cuda and x_bta.dtype in (torch.float16, torch.bfloat16):
+        x_bta = x_bta.float()
+    _check(x_bta, "world_unnormalize_v2")
+    x_bta = x_bta.contiguous()
+    B, T, A = x_bta.shape
+    S, cap = ls_mean.shape[0], ca_mean.shape[0]
+    if A != 2 + S + 2 * cap:
+        raise RuntimeError(f"world_unnormalize_v2: x has {A} features, the norm implies {2 + S + 2 * cap}")
+    f0 = _f32(B, T, like=x_bta)
+    logspc = _f32(B, T, S, like=x_bta)
+    codeap = _f32(B, T, cap, like=x_bta)
+    nv = [t.detach().float().contiguous() for t in (f0_mean, f0_std, ls_mean, ls_std, ca_mean, ca_std)]
+    N.call("v100_world_unnormalize_v2", x_bta, f0, logspc, codeap, *nv, B, T, S, cap)
+    return f0, logspc, codeap
+
+
+class WorldLossV2Fn(torch.autograd.Function):
+    """The v2 WORLDLoss (voice100/models/_layers_v2.py:116-163) with AlignTextToAudio's target preparation (_tts_v2.py:98-101) on
+    the projection output pred [B, Tp, 2+S+2Cap]: one HIP pass for the five terms AND their gradient (v100_world_loss_v2), from the
+    RAW targets and the six WORLDNorm vectors; backward is one scaling kernel."""
+
+    @staticmethod
+    def forward(ctx, pred, length, f0, logspc, codeap, norm, l1):
+        _check(pred, "world_loss_v2")
+        pred = pred.contiguous()
+        B, Tp, A = pred.shape
+        S, cap = logspc.shape[2], codeap.shape[2]
+        if A != 2 + S + 2 * cap:
+            raise RuntimeError(f"world_loss_v2: pred has {A} features, targets imply {2 + S + 2 * cap}")
+        Tt = f0.shape[1]
+        dev = pred.device
+        f0, logspc, codeap = (t.to(device=dev, dtype=torch.float32).contiguous() for t in (f0, logspc, codeap))
+        if logspc.shape[1] != Tt or codeap.shape[1] != Tt or f0.shape[0] != B or logspc.shape[0] != B or codeap.shape[0] != B:
+            raise RuntimeError("world_loss_v2: targets must be [B, Tt(, C)] with one time axis")
+        length = length.to(device=dev, dtype=torch.int32).contiguous()
+        if length.shape != (B,):
+            raise RuntimeError("world_loss_v2: length must be [B]")
+        nrm = [t.detach().to(device=dev, dtype=torch.float32).contiguous() for t in norm]
+        partial = _f32(N.helper("v100_world_loss_parts", B, Tp), 5, like=pred)
+        loss = _f32(5, like=pred)
+        unit = torch.empty_like(pred)
+        N.call("v100_world_loss_v2", pred, f0, logspc, codeap, length, *nrm, partial, loss, unit, B, Tp, Tt, S, cap, int(l1))
+        ctx.save_for_backward(unit)
+        ctx.dims = (B, Tp, S, cap)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        (unit,) = ctx.saved_tensors
+        B, Tp, S, cap = ctx.dims
+        dpred = torch.empty_like(unit)
+        N.call("v100_world_loss_v2_bwd", unit, gout.to(torch.float32).contiguous(), dpred, B, Tp, S, cap)
+        return (dpred,) + (None,) * 6
+
+
+def world_loss_v2(pred_bta, length, f0, logspc, codeap, norm, loss: str = "mse"):
+    """The five v2 WORLDLoss terms (hasf0, f0, logspc, hascodeap, codeap) as a [5] tensor.  f0 / logspc / codeap are the RAW
+    WORLD features; `norm` is (f0_mean, f0_std, logspc_mean, logspc_std, codeap_mean, codeap_std)."""
+    if loss not in ("l1", "mse"):
+        raise ValueError("Unknown loss type")
+    return WorldLossV2Fn.apply(pred_bta, length, f0, logspc, codeap, tuple(norm), loss == "l1")
+
+
+class AlignLossFn(torch.autograd.Function):
+    """TextToAlignText's loss (_align_v2.py:80-88): masked mean over text_len of mean_k |log(align + 1) - pred|, value and gradient
+    in one HIP pass (v100_align_loss); backward scales the saved unit gradient (v100_align_loss_bwd)."""
+
+    @staticmethod
+    def forward(ctx, pred, align, text_len):
+        _check(pred, "align_loss")
+        pred = pred.contiguous()
+        B, L, two = pred.shape
+        if two != 2:
+            raise RuntimeError("align_loss: pred must be [B, L, 2]")
+        dev = pred.device
+        align = align.to(device=dev, dtype=torch.int64).contiguous()
+        W = align.shape[1]
+        if align.shape[0] != B or W - 1 != 2 * L:
+            raise RuntimeError(f"align_loss: align [B, 2L+1] = [{B}, {2 * L + 1}] expected, got {list(align.shape)}")
+        text_len = text_len.to(device=dev, dtype=torch.int32).contiguous()
+        partial = _f32(N.helper("v100_align_loss_parts", B, L), like=pred)
+        loss = _f32(1, like=pred)
+        unit = torch.empty_like(pred)
+        N.call("v100_align_loss", pred, align, text_len, partial, loss, unit, B, L, W)
+        ctx.save_for_backward(unit)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        (unit,) = ctx.saved_tensors
+        B, L, _ = unit.shape
+        dpred = torch.empty_like(unit)
+        N.call("v100_align_loss_bwd", unit, gout.to(torch.float32).reshape(1).contiguous(), dpred, B, L)
+        return dpred, None, None
+
+
+def align_loss(pred_bl2, align, text_len):
+    """pred [B, L, 2], align [B, 2L+1] int64 (gap, len pairs and one trailing entry), text_len [B] -> 0-dim loss."""
+    return AlignLossFn.apply(pred_bl2, align, text_len)
+
+
 class CTCLossFn(torch.autograd.Function):
     """log_softmax(dim=-1) + CTCLoss(blank=0, reduction='mean', zero_infinity=True) on logits [B, T, V]
     (asr.py:146-152), forward and gradient in one pass of the HIP lattice kernels.  Limits of the kernel: V <= 128 classes,

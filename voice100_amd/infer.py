@@ -18,7 +18,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
-__all__ = ["shard_indices", "scatter_run", "TTSPipeline", "ASRPipeline", "GraphedForward"]
+__all__ = ["shard_indices", "scatter_run", "TTSPipeline", "TTSPipelineV2", "ASRPipeline", "GraphedForward"]
 
 
 def shard_indices(n_items: int, rank: int, world: int, mode: str = "contiguous") -> torch.Tensor:
@@ -145,6 +145,49 @@ class TTSPipeline:
         spc = v.logspc_to_spc(logspc) if v is not None else None
         # valid WORLD frames per utterance: 2 * len - 1 (update_samples.py:81 slices 2 * len, which yields the same)
         frames = torch.clamp_min(2 * at_len - 1, 0)
+        out = {"align": align, "aligntext": aligntext, "aligntext_len": at_len, "f0": f0, "logspc": logspc, "spc": spc,
+               "codeap": codeap, "frames": frames}
+        if v is not None and self.synthesize and v.n_fft == 512 and f0.shape[1] >= 2:
+            wave, npulses = v.synthesize(f0, spc, frames=frames, f0_ceil=self.f0_ceil, codeap=codeap)
+            out["wave"], out["n_pulses"] = wave, npulses
+            out["wave_len"] = (frames.to(torch.float64) * v.frame_period * v.sample_rate / 1000).to(torch.int64)
+        return out
+
+
+class TTSPipelineV2:
+    """The v2 sample chain (update_samples.py:50-80) on the device:
+
+        text [B, L] int64, text_len [B]
+          -> TextToAlignText.predict                       align [B, max(text_len), 2] = exp(pred) - 1, unclamped  (_align_v2.py:39-46)
+          -> align() batched, on the device                aligntext [B, max n] int64 zero padded (pad_sequence width), n [B]
+                                                           (_align_v2.py:48-73, v100_align_expand_v2)
+          -> AlignTextToAudio.predict                      f0 [B, 2 max(n) - 1], logspc|mcep, codeap, gated   (_tts_v2.py:80-94)
+          -> (use_mcep) logspc = mcep @ mc2sp              one fp32 MFMA GEMM over all B x T frames           (vocoder.py:95)
+          -> optionally synthesize, frames = min(2 n, 2 max(n) - 1) per utterance   (update_samples.py:80-84 slices [:2 n])
+
+    The existing TTSPipeline (the v1 models) is unchanged."""
+
+    def __init__(self, align_model, audio_model, vocoder=None, head: int = 5, tail: int = 5, synthesize: bool = True,
+                 f0_ceil: float = 1000.0):
+        self.align_model, self.audio_model, self.vocoder = align_model, audio_model, vocoder
+        self.head, self.tail = head, tail
+        self.synthesize, self.f0_ceil = synthesize, f0_ceil
+
+    @torch.no_grad()
+    def __call__(self, text: torch.Tensor, text_len: torch.Tensor):
+        from .decode import align_expand_v2
+        align, align_len = self.align_model.predict(text, text_len)         # [B, max(text_len), 2]
+        L = align.shape[1]
+        aligntext, at_len = align_expand_v2(text[:, :L], align, align_len, self.head, self.tail)
+        f0, feat, codeap = self.audio_model.predict(aligntext, at_len)       # 2 * max(n) - 1 frames
+        v = self.vocoder
+        if v is not None and v.use_mcep:
+            B, T, C = feat.shape
+            logspc = v.mcep_to_logspc(feat.reshape(B * T, C)).reshape(B, T, -1)
+        else:
+            logspc = feat
+        spc = v.logspc_to_spc(logspc) if v is not None else None
+        frames = torch.clamp_max(2 * at_len, f0.shape[1])
         out = {"align": align, "aligntext": aligntext, "aligntext_len": at_len, "f0": f0, "logspc": logspc, "spc": spc,
                "codeap": codeap, "frames": frames}
         if v is not None and self.synthesize and v.n_fft == 512 and f0.shape[1] >= 2:
