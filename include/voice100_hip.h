@@ -505,8 +505,12 @@ int v100_world_d4c(const float* x, const int* lengths, const double* f0, int B, 
  *   the outputs are then invalid and the caller raises.
  *   use_bf16: 0 exact fp32 MFMA, 1 bf16 operands, 2 fp16 operands (inference only); fp32 accumulate and fp32 cell state in every mode.
  *   persistent: 1 = one launch for all steps when the grid is resident (v100_lstm_persistent_ok), else one launch per step; 0 = one
- *   launch per step.  Both forms compute bit-identical results. */
+ *   launch per step.  Both forms compute bit-identical results.
+ *   v100_lstm_geometry (host only, no GPU): out[4] = {U hidden units per workgroup, G = H / U workgroups per (direction, 16-sequence
+ *   slice), 1 if the W_hh slice is staged in LDS (else read from global memory: step form only), dynamic LDS bytes per workgroup} of
+ *   the forward (backward = 0) or backward recurrence; 1 for a shape v100_lstm_fwd / v100_lstm_bwd reject (fp16 has no backward). */
 long long v100_lstm_weight_bytes(int H, int ndir, int use_bf16, int backward);
+int v100_lstm_geometry(int H, int use_bf16, int backward, int* out);
 long long v100_lstm_ws_bytes(int B, int H, int ndir, int backward);
 int v100_lstm_sync_words(int B, int ndir);
 int v100_lstm_persistent_ok(int B, int H, int ndir, int use_bf16, int backward);

@@ -1,4 +1,6 @@
 """GPU checks of the HIP LSTM (K15) and AudioToAlignText against torch.nn.LSTM in float64 on the CPU and the reference fixture."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -31,11 +33,11 @@ def _lengths(B, T):
     return lens
 
 
-def _case(C, H, B, T, layers, bidir, seed=0):
+def _case(C, H, B, T, layers, bidir, seed=0, bias=True, lens=None):
     torch.manual_seed(seed)
-    ref = nn.LSTM(C, H, num_layers=layers, bidirectional=bidir)
+    ref = nn.LSTM(C, H, num_layers=layers, bias=bias, bidirectional=bidir)
     x = torch.randn(T, B, C)
-    lens = _lengths(B, T)
+    lens = _lengths(B, T) if lens is None else torch.tensor(lens)
     D = 2 if bidir else 1
     gy = torch.randn(T, B, D * H)
     gh = torch.randn(layers * D, B, H)
@@ -44,7 +46,7 @@ def _case(C, H, B, T, layers, bidir, seed=0):
 
 
 def _oracle(ref, x, lens, gy, gh, gc, dtype=torch.float64, device="cpu", autocast=False):
-    m = nn.LSTM(ref.input_size, ref.hidden_size, num_layers=ref.num_layers, bidirectional=ref.bidirectional)
+    m = nn.LSTM(ref.input_size, ref.hidden_size, num_layers=ref.num_layers, bias=ref.bias, bidirectional=ref.bidirectional)
     m.load_state_dict(ref.state_dict())
     m = m.to(device=device, dtype=dtype)
     xx = x.to(device=device, dtype=dtype).requires_grad_(True)
@@ -61,7 +63,7 @@ def _oracle(ref, x, lens, gy, gh, gc, dtype=torch.float64, device="cpu", autocas
 
 
 def _mine(ref, x, lens, gy, gh, gc, cuda, lens_on_device=False):
-    m = LSTM(ref.input_size, ref.hidden_size, num_layers=ref.num_layers, bidirectional=ref.bidirectional).to(cuda)
+    m = LSTM(ref.input_size, ref.hidden_size, num_layers=ref.num_layers, bias=ref.bias, bidirectional=ref.bidirectional).to(cuda)
     m.load_state_dict(ref.state_dict())
     xx = x.to(cuda).requires_grad_(True)
     out, (h, c) = m(xx, lengths=lens.to(cuda) if lens_on_device else lens)
@@ -133,14 +135,14 @@ def _layer_inputs(cuda, B=20, C=48, H=64, T=17, seed=5):
 def test_persistent_bit_identical_to_step_form(cuda, precision):
     F_.set_matmul_precision(precision)
     fmt = 1 if precision == "bf16" else 0
-    for H in (48, 64, 512):
-        x, lens, params = _layer_inputs(cuda, H=H, T=9 if H == 512 else 17)
-        B = x.shape[0]
-        assert all(N.helper("v100_lstm_persistent_ok", B, H, 2, fmt, bwd) for bwd in (0, 1)), H      # the two forms really differ
+    # B = 40 and 128: several slices, the last one ragged (40) or the grid at the persistent form's 128-workgroup cap (128)
+    for B, H, T in ((20, 48, 17), (20, 64, 17), (20, 512, 9), (40, 256, 12), (128, 256, 9)):
+        x, lens, params = _layer_inputs(cuda, B=B, H=H, T=T)
+        assert all(N.helper("v100_lstm_persistent_ok", B, H, 2, fmt, bwd) for bwd in (0, 1)), (B, H)      # the two forms really differ
         a = _run_layer(cuda, x, lens, params, persistent=True)
         b = _run_layer(cuda, x, lens, params, persistent=False)
         for i, (u, v) in enumerate(zip(a, b)):
-            assert torch.equal(u, v), (H, i)
+            assert torch.equal(u, v), (B, H, i)
 
 
 def test_two_calls_bit_identical(cuda):
@@ -333,3 +335,150 @@ def test_asr_v2_ctc_best_path_matches_reference(cuda):
     assert np.array_equal(path.cpu().numpy(), g["best/path"])
     assert np.array_equal(lens.cpu().numpy(), g["best/logits_len"])
     assert np.array_equal(score.cpu().numpy(), g["best/score"])
+
+
+# ---- Regime sweep: every launch regime lstm.hip's ls_geometry / ls_launch choose, against fp64 nn.LSTM ----------------------------
+# A regime is (U hidden units per workgroup, W_hh slice in LDS, grid = ndir * ceil(B / 16) * G, persistent form).  Each case asserts
+# the regime it is meant for before it compares anything, so a later change of the geometry fails here instead of moving the case
+# onto another code path.  The regime does not depend on T: T is short except where the length is the point.
+
+def _geometry(H, fmt, backward):
+    out = (ctypes.c_int * 4)()
+    assert N.helper("v100_lstm_geometry", H, fmt, backward, out) == 0, (H, fmt, backward)
+    return dict(zip(("U", "G", "wlds", "lds"), out))
+
+
+def _assert_regime(B, H, ndir, fmt, regime, directions=(0, 1)):
+    for bwd in directions:
+        g = _geometry(H, fmt, bwd)
+        got = (g["U"], bool(g["wlds"]), ndir * -(-B // 16) * g["G"], bool(N.helper("v100_lstm_persistent_ok", B, H, ndir, fmt, bwd)))
+        assert got == regime, (f"the {('forward', 'backward')[bwd]} recurrence at B = {B}, H = {H}, fmt {fmt} runs as {got}; "
+                               f"the case is meant for {regime} (U, W_hh in LDS, grid, persistent)")
+
+
+def _spy_launches(monkeypatch):
+    """[(entry point, kernel launches it issued)] of every recurrence call: 1 for the persistent form, T for the step form."""
+    seen = []
+    real = N.call
+
+    def spy(name, *args):
+        if name not in ("v100_lstm_fwd", "v100_lstm_bwd"):
+            return real(name, *args)
+        n0 = N.launch_count()
+        real(name, *args)
+        seen.append((name, N.launch_count() - n0))
+    monkeypatch.setattr(N, "call", spy)
+    return seen
+
+
+_ORACLES = {}
+
+
+def _cached_oracle(shape, bias=True, lens=None, seed=0):
+    """The case and its fp64 oracle, computed once per module for the precisions that share it."""
+    key = (shape, bias, lens, seed)
+    if key not in _ORACLES:
+        case = _case(*shape, seed=seed, bias=bias, lens=lens)
+        _ORACLES[key] = case, _oracle(*case)
+    return _ORACLES[key]
+
+
+def _assert_bf16_close(mine, yard, exact):
+    """bf16 against fp64, bounded as test_bf16_against_fp16_autocast_nn_lstm bounds it: < 2e-2 and < 5x the fp16-autocast error."""
+    y, h, c, g = mine
+    ay, ah, ac, ag = yard
+    ry, rh, rc, rg = exact
+    for what, m, a, r in [("y", y, ay, ry), ("h_n", h, ah, rh), ("c_n", c, ac, rc)] + [("grad " + k, g[k], ag[k], rg[k]) for k in rg]:
+        e, e16 = rel_l2(m, r), rel_l2(a, r)
+        print(f"{what}: bf16 {e:.2e}  fp16-autocast nn.LSTM {e16:.2e}")
+        assert e < 2e-2 and e < 5 * e16 + 1e-4, what
+
+
+P, S = True, False         # the persistent form / the step form
+SWEEP = [  # id, (C, H, B, T, layers, bidirectional), bias, lengths (None: _lengths), precision, regime of forward and backward
+    ("h80-U16", (40, 80, 5, 13, 2, True), True, None, "fp32", (16, True, 10, P)),                 # U = 16 as H % 32 != 0, one slice
+    ("h48-U16-ragged", (48, 48, 20, 17, 1, True), True, None, "fp32", (16, True, 12, P)),         # 2nd slice holds 4 sequences
+    ("b40-3slices", (64, 256, 40, 12, 1, True), True, None, "fp32", (32, True, 48, P)),           # last slice 8 wide
+    ("unidir-b17", (64, 64, 17, 9, 2, False), True, None, "fp32", (32, True, 4, P)),              # 2nd slice holds 1 sequence
+    ("align_en_base-fp32", (256, 256, 128, 20, 1, True), True, None, "fp32", (32, True, 128, P)),  # 8 slices, grid at the cap
+    ("align_en_base-bf16", (256, 256, 128, 20, 1, True), True, None, "bf16", (32, True, 128, P)),
+    ("step-lds-b33", (64, 512, 33, 12, 1, True), True, None, "fp32", (16, True, 192, S)),         # 3rd slice holds 1 sequence
+    ("tts_en_base-fp32", (512, 512, 128, 16, 1, True), True, None, "fp32", (16, True, 512, S)),
+    ("tts_en_base-bf16", (512, 512, 128, 16, 1, True), True, None, "bf16", (32, True, 256, S)),
+    ("h1024-bf16", (32, 1024, 17, 6, 1, True), True, None, "bf16", (16, True, 256, S)),            # backward: K = 4096 slice in LDS
+    ("long-bf16", (512, 512, 4, 512, 1, True), True, (512, 300, 1, 77), "bf16", (32, True, 32, P)),
+    ("nobias-fp32", (24, 32, 20, 9, 2, True), False, None, "fp32", (32, True, 4, P)),
+    ("nobias-bf16", (24, 32, 20, 9, 2, True), False, None, "bf16", (32, True, 4, P)),
+]
+
+
+@pytest.mark.parametrize("shape,bias,lens,precision,regime", [c[1:] for c in SWEEP], ids=[c[0] for c in SWEEP])
+def test_regime_sweep_against_fp64(cuda, monkeypatch, shape, bias, lens, precision, regime):
+    C, H, B, T, layers, bidir = shape
+    fmt = {"fp32": 0, "bf16": 1}[precision]
+    _assert_regime(B, H, 2 if bidir else 1, fmt, regime)
+    case, exact = _cached_oracle(shape, bias, lens)
+    yard = _oracle(*case, dtype=torch.float32, device=cuda, autocast=True) if fmt else None
+    F_.LSTM_PERSISTENT = True
+    F_.set_matmul_precision(precision)
+    launches = _spy_launches(monkeypatch)
+    mine = _mine(*case, cuda)
+    per_call = 1 if regime[3] else T
+    assert launches == [("v100_lstm_fwd", per_call)] * layers + [("v100_lstm_bwd", per_call)] * layers, launches
+    if fmt:
+        _assert_bf16_close(mine, yard, exact)
+        return
+    y, h, c, g = mine
+    ry, rh, rc, rg = exact
+    assert rel_err(y, ry) < 1e-4
+    assert rel_err(h, rh) < 1e-4
+    assert rel_err(c, rc) < 1e-4
+    assert_grads_close(g, rg, 1e-4)
+
+
+@pytest.mark.parametrize("shape,regime", [
+    ((512, 512, 128, 16, 1, True), (32, True, 256, S)),            # tts_en_base width: step form
+    ((256, 256, 128, 20, 1, True), (32, True, 128, P)),            # align_en_base width: persistent form at the cap
+], ids=["step", "persistent-cap"])
+def test_fp16_eval_regimes(cuda, monkeypatch, shape, regime):
+    C, H, B, T, layers, bidir = shape
+    _assert_regime(B, H, 2 if bidir else 1, 2, regime, directions=(0,))
+    (ref, x, lens, _, _, _), (ry, rh, rc, _) = _cached_oracle(shape)
+    m = LSTM(C, H, num_layers=layers, bidirectional=bidir).to(cuda).eval()
+    m.load_state_dict(ref.state_dict())
+    F_.LSTM_PERSISTENT = True
+    F_.set_matmul_precision("fp16")
+    launches = _spy_launches(monkeypatch)
+    with torch.no_grad():
+        y, (h, c) = m(x.to(cuda), lengths=lens)
+    assert launches == [("v100_lstm_fwd", 1 if regime[3] else T)] * layers, launches
+    for mine, exact in ((y, ry), (h, rh), (c, rc)):
+        assert rel_l2(mine, exact) < 2e-3
+
+
+def test_padded_beyond_longest_sequence(cuda, monkeypatch):
+    """T = 15 with every length <= 11: y and the input gradient are exactly 0 beyond each length, and h_n / c_n are each sequence's
+    own last step (direction 1 starts at len - 1, not at T - 1)."""
+    shape = C, H, B, T, layers, bidir = (48, 64, 20, 15, 2, True)
+    g = torch.Generator().manual_seed(31)
+    lens = torch.randint(1, 12, (B,), generator=g)
+    lens[0], lens[1] = 11, 1
+    lens = tuple(int(v) for v in lens)
+    _assert_regime(B, H, 2, 0, (32, True, 8, P))
+    case, (ry, rh, rc, rg) = _cached_oracle(shape, lens=lens)
+    F_.LSTM_PERSISTENT = True
+    launches = _spy_launches(monkeypatch)
+    y, h, c, gr = _mine(*case, cuda)
+    assert launches == [("v100_lstm_fwd", 1)] * layers + [("v100_lstm_bwd", 1)] * layers, launches
+    assert rel_err(y, ry) < 1e-4 and rel_err(h, rh) < 1e-4 and rel_err(c, rc) < 1e-4
+    assert_grads_close(gr, rg, 1e-4)
+    pad = torch.arange(T)[:, None] >= torch.tensor(lens)[None, :]           # [T, B]
+    assert torch.all(y[pad] == 0)
+    assert torch.all(gr["x"][pad] == 0)
+    ref, x = case[0], case[1]
+    m = nn.LSTM(C, H, num_layers=layers, bidirectional=bidir).double()
+    m.load_state_dict(ref.state_dict())
+    with torch.no_grad():
+        for b, n in enumerate(lens):                  # each sequence alone, unpadded, in fp64
+            _, (hb, cb) = m(x[:n, b:b + 1].double())
+            assert rel_err(h[:, b], hb[:, 0]) < 1e-4 and rel_err(c[:, b], cb[:, 0]) < 1e-4, b

@@ -1,5 +1,6 @@
 """CPU-side checks of the LSTM module and the v2 ASR model (K15): parameter names, shapes and initialisation are nn.LSTM's and
 the reference's, unsupported options raise, nothing runs on the CPU, and the library exports the recurrence's entry points."""
+import ctypes
 import re
 
 import pytest
@@ -73,7 +74,7 @@ def test_header_exports_lstm_symbols():
     lib = N.load()
     text = open(N.HEADER_PATH).read()
     names = ["v100_lstm_weight_bytes", "v100_lstm_ws_bytes", "v100_lstm_sync_words", "v100_lstm_persistent_ok",
-             "v100_lstm_weight_prep", "v100_lstm_fwd", "v100_lstm_bwd"]
+             "v100_lstm_weight_prep", "v100_lstm_fwd", "v100_lstm_bwd", "v100_lstm_geometry"]
     for n in names:
         assert re.search(r"\b%s\s*\(" % n, text), n
         assert hasattr(lib, n), n
@@ -85,6 +86,55 @@ def test_header_exports_lstm_symbols():
     assert lib.v100_lstm_bwd(*([None] * 10), 1, 1, 32, 1, 0, 1, None) == 3
     assert lib.v100_lstm_weight_prep(None, None, 32, 1, 0, 0, None, None) == 3
     assert lib.v100_lstm_weight_bytes(40, 1, 0, 0) == 0
+
+
+def _geometry(lib, H, fmt, backward):
+    out = (ctypes.c_int * 4)()
+    assert lib.v100_lstm_geometry(H, fmt, backward, out) == 0, (H, fmt, backward)
+    return dict(zip(("U", "G", "wlds", "lds"), out))
+
+
+# (fmts, directions, H, U, W_hh in LDS or None for either): the regimes tests/test_gpu_lstm.py's sweep relies on
+LSTM_REGIMES = [
+    ((0,), (0,), 512, 16, 1),         # fp32 forward at the tts_en_base width: the U = 32 slice does not fit the LDS
+    ((0,), (1,), 512, 16, 1),
+    ((1,), (0,), 512, 32, 1),
+    ((0,), (0, 1), 1024, 16, 0),      # fp32 at H = 1024: W_hh read from global memory, step form only
+    ((1,), (0, 1), 1024, 16, 1),      # bf16 at H = 1024: the backward keeps a K = 4096 slice in LDS
+    ((0, 1, 2), (0, 1), 48, 16, None),
+    ((0, 1, 2), (0, 1), 80, 16, None),
+    ((0,), (0,), 256, 32, 1),         # align_en_base
+    ((1,), (0,), 256, 32, 1),
+]
+
+
+def test_lstm_geometry_regimes_and_invariants():
+    from voice100_amd import _native as N
+    import __graft_entry__
+    import os
+    if not os.path.exists(N.LIB_PATH):
+        __graft_entry__.build()
+    lib = N.load()
+    for fmts, dirs, H, U, wlds in LSTM_REGIMES:
+        for fmt in fmts:
+            for bwd in dirs:
+                if bwd and fmt == 2:
+                    continue                          # fp16 is an inference precision
+                g = _geometry(lib, H, fmt, bwd)
+                assert g["U"] == U, (fmt, bwd, H, g)
+                assert wlds is None or g["wlds"] == wlds, (fmt, bwd, H, g)
+    for fmt, bwd in [(0, 0), (1, 0), (2, 0), (0, 1), (1, 1)]:
+        for H in range(16, 1025, 16):
+            g = _geometry(lib, H, fmt, bwd)
+            assert g["U"] in (16, 32) and H % g["U"] == 0 and g["G"] * g["U"] == H, (fmt, bwd, H, g)
+            assert g["lds"] > 0 and (not g["wlds"] or g["lds"] <= 160 * 1024), (fmt, bwd, H, g)
+            for ndir in (1, 2):
+                wb = lib.v100_lstm_weight_bytes(H, ndir, fmt, bwd)
+                assert wb > 0 and wb % (ndir * g["G"]) == 0, (fmt, bwd, H, ndir, wb, g)
+    out = (ctypes.c_int * 4)()
+    for H, fmt, bwd in [(0, 0, 0), (8, 0, 0), (40, 0, 0), (1040, 0, 0), (2048, 1, 1), (64, -1, 0), (64, 3, 0), (64, 2, 1)]:
+        assert lib.v100_lstm_geometry(H, fmt, bwd, out) == 1, (H, fmt, bwd)
+    assert lib.v100_lstm_geometry(64, 0, 0, None) == 3
 
 
 def test_traced_forward_is_stock_lstm():

@@ -451,6 +451,14 @@ extern "C" long long v100_lstm_weight_bytes(int H, int ndir, int use_bf16, int b
     return (long long)ndir * g.G * g.wbytes;
 }
 
+extern "C" int v100_lstm_geometry(int H, int use_bf16, int backward, int* out) {
+    if (!out) return V100_ERR_NULL;
+    if (H < 16 || H > 1024 || H % 16 || use_bf16 < 0 || use_bf16 > 2 || (backward && use_bf16 == 2)) return V100_ERR_SHAPE;
+    const Geo g = ls_geometry(H, use_bf16, backward ? 1 : 0);
+    out[0] = g.U; out[1] = g.G; out[2] = g.wlds; out[3] = g.lds;
+    return V100_OK;
+}
+
 extern "C" long long v100_lstm_ws_bytes(int B, int H, int ndir, int backward) {
     if (B < 1 || H < 16 || ndir < 1 || ndir > 2) return 0;
     const long long xk = backward ? 4LL * H : H;
