@@ -54,7 +54,7 @@ def check_abs(got, ref, what, bound):
 
 
 def splits_rule(B, M, K):
-    """v100_pw_wgrad_splits restated (csrc/pointwise.hip; V100_WG_TARGET unset): -> (S, TS), TS = 0 in the batch-split regime"""
+    """v100_pw_wgrad_splits restated (csrc/pointwise.hip): -> (S, TS), TS = 0 in the batch-split regime"""
     tiles = -(-M // 128) * -(-K // 128)
     S = -(-512 // tiles)
     if S <= B:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the short-K GEMMs of the training step (expand forward, project backward-data; 256- and 512-wide blocks) for ONE library
-build (timing-only ablation builds included: results are not checked), rotating buffer sets as tools/gemm_yardstick.py does.
+build (results are not checked), rotating buffer sets as tools/gemm_yardstick.py does.
 usage: python tools/ab_ov.py [--lib build/variants/lib_X.so] [--iters 48]"""
 import argparse
 import os

@@ -17,7 +17,6 @@
 // 128x128 block tile, 4 waves as 2x2, each wave 64x64 = 2x2 MFMA 32x32 tiles (64 acc VGPRs).
 // 1-D grid with an XCD-aware remap: the M-tiles that share one X tile run on one XCD (one L2).
 #include "pointwise_common.h"
-#include <stdlib.h>
 #include "timing.h"
 
 void pw_launch_gemm_f32(const PwParams& p, dim3 grid, hipStream_t st);
@@ -79,8 +78,7 @@ extern "C" int v100_pw_num_parts(int B, int T) { return B * ceil_div(T, PW_BN); 
 extern "C" int v100_pw_wgrad_splits(int B, int M, int K) {
     // enough (tile, split) workgroups to fill the chip, capped by the batch
     const int tiles = ceil_div(M, PW_BM) * ceil_div(K, PW_BN);
-    static const int target = [] { const char* e = getenv("V100_WG_TARGET"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
-    int S = ceil_div(target, tiles);
+    int S = ceil_div(512, tiles);     // (256 and 1024 workgroups as the aim: rejected, DESIGN_rejected.md)
     if (S > B) {
         // fewer (tile, utterance) pairs than the chip has CUs (the 64 -> 256 opener's two tiles, the vocabulary head): split each
         // utterance's t range too -- S = B * TS, TS a power of two <= 8 with one workgroup per CU as the aim (WgSpan, pointwise_common.h)

@@ -26,94 +26,6 @@ enum { PW_EPI_STORE = 0, PW_EPI_STATS = 1, PW_EPI_AFFINE_RELU6 = 2, PW_EPI_AFFIN
 #define PW_BM 128
 #define PW_BN 128
 
-// Timing-only ablation builds (tools/ab_variants.sh PW_ABLATE ...): bit 0 drops the X loads, bit 1 the A loads (zero-record
-// buffer descriptors: same instruction stream, no traffic), bit 2 the epilogue's global stores.  0 in the product.
-#ifndef PW_ABLATE
-#define PW_ABLATE 0
-#endif
-#ifndef PW_EPI_FAST
-#define PW_EPI_FAST 2      /* 1: lean epilogue for interior tiles; 2: also for the partial last t-tile (PT) */
-#endif
-#ifndef PW_LAT
-#define PW_LAT 1             /* latency form of the inference GEMMs when the matrix has too few 256 x 128 tiles to fill the chip */
-#endif
-#ifndef PW_LAT_MAXTILES
-#define PW_LAT_MAXTILES 64
-#endif
-#ifndef PW_LAT_NSTG
-#define PW_LAT_NSTG 4
-#endif
-#ifndef PW_PERSIST
-#define PW_PERSIST 1         /* persistent workgroups with cross-tile prefetch for the short-K training GEMMs */
-#endif
-#ifndef PW_WG_EXPAND_NST
-#define PW_WG_EXPAND_NST 3    /* register staging of the expand backward-weight kernel: 1 one stage, 2 two (spills), 3 two for G + one for X */
-#endif
-#ifndef PW_WG_WIDE
-#define PW_WG_WIDE 1         /* 256 x 128 backward-weight tiles for the act16 combinations (0: the 128 x 128 kernel everywhere) */
-#endif
-#ifndef PW_WS
-#define PW_WS 7              /* wave-specialised NN GEMM (pw_gemm_bf16_ws_kernel): bit x_mode set = that prologue family uses it.  With
-                                PW_WS_MINK = 1024 that is: project forward and expand backward-data (transform on load, K = the hidden
-                                width) in training, the eval-mode project GEMM (plain bf16 h2, K = the hidden width) in inference */
-#endif
-#ifndef PW_OV
-#define PW_OV 1              /* short-K GEMMs with the epilogue under the next tile's main loop (pw_gemm_bf16_ov_kernel): expand forward */
-#endif
-#ifndef PW_OV_MASK
-#define PW_OV_MASK 1         /* ... and project backward-data (mask epilogue) */
-#endif
-#ifndef PW_SL
-#define PW_SL 4              /* split-role short-K GEMM (pw_gemm_bf16_sl_kernel) instead of the overlapped-epilogue one: bit 0 expand forward
-                                K = 512, bit 1 K = 256, bit 2 project backward-data K = 512, bit 3 K = 256 */
-#endif
-#ifndef PW_SL_PRIO
-#define PW_SL_PRIO 3
-#endif
-#ifndef PW_SL_RAWBAR
-#define PW_SL_RAWBAR 1
-#endif
-#ifndef PW_OV_RAWBAR
-#define PW_OV_RAWBAR 0       /* the overlapped-epilogue kernel's k-tile barrier as s_waitcnt lgkmcnt(0) + s_barrier (no vmcnt(0)) */
-#endif
-#ifndef PW_SL_DBG
-#define PW_SL_DBG 0
-#endif
-#ifndef PW_OV_XTR
-#define PW_OV_XTR 1          /* round 5: the overlapped-epilogue kernel keeps its X image [k][t] as loaded (16-byte copies) and reads the B
-                                fragments with ds_read_b64_tr_b16 (0: [t][k] image built with byte permutes + 8-byte column stores) */
-#endif
-#ifndef PW_OV_TOUCH
-#define PW_OV_TOUCH 0        /* overlapped-epilogue kernel: L2 touch of a tile's R lines (bit 0) / Y lines (bit 1) at the start of its k-loop */
-#endif
-#ifndef PW_OV_CP_Y
-#define PW_OV_CP_Y 0         /* cache policy (buffer aux bits) of the overlapped-epilogue kernel's Y stores: 1 sc0, 2 nt, 3 both */
-#endif
-#ifndef PW_OV_ABL
-#define PW_OV_ABL 0          /* timing-only builds of pw_gemm_bf16_ov_kernel (WRONG results): 1 no epilogue, 2 no X staging, 4 no A staging,
-                                8 no barrier, 16 no fragment reads, 32 no Y stores, 64 no statistics (partial sums through LDS), 128 no R loads */
-#endif
-#ifndef PW_OV_GAP
-#define PW_OV_GAP 8
-#endif
-#ifndef PW_WG_ABL
-#define PW_WG_ABL 0          /* timing-only builds of pw_wgrad_bf16_ws_kernel: 1 / 2 every plain / transformed load re-reads the first tile, 4 no
-                                transform, 8 staging waves: loads only, 16 no MFMA */
-#endif
-#ifndef PW_WG_WS
-#define PW_WG_WS 3           /* wave-specialised backward-weight kernel (pw_wgrad_bf16_ws_kernel), all-bf16 act16 combinations: bit 0 the project
-                                gradient, bit 1 the expand gradient; bits 2 / 3: eight staging waves instead of four for the former / latter */
-#endif
-#ifndef PW_WS_ABL
-#define PW_WS_ABL 0
-#endif
-#ifndef PW_WS_MINK
-#define PW_WS_MINK 1024      /* ... at K >= this (shorter K: the persistent / 128-row forms of the 8-wave kernel win, profiles/r03_ws_gemm.txt) */
-#endif
-#ifndef PW_BM128_MAXK
-#define PW_BM128_MAXK 0      /* A/B knob: 128-row tiles (two workgroups per CU) for GEMMs with K <= this */
-#endif
-
 struct PwParams {
     const float* A;       // [M][K] fp32 weights
     const u16* Abf;       // [M][K] bf16 weights (bf16 path)
@@ -291,17 +203,7 @@ __device__ __forceinline__ float half_wave_sum_dpp(float v) {
 // all 16 passes in flight before the accumulators go through LDS, statistics written once at the end.
 // PT: the tile's rows all lie inside the tensor but its last columns do not (t0 + 128 > T: the last t-tile of a time-stretched length):
 // same path with a per-lane column test -- lanes past T neither store nor count; a lane that straddles T masks per element.
-// cache policy of the epilogue's big streams (A/B: -DPW_EPI_CP_Y=2 / -DPW_EPI_CP_R=2 = nontemporal): Y is written once and read by
-// the NEXT kernel, R is read once
-#ifndef PW_EPI_CP_Y
-#define PW_EPI_CP_Y 0
-#endif
-#ifndef PW_EPI_STATS_LDS
-#define PW_EPI_STATS_LDS 1    /* lean epilogue: BatchNorm partial sums reduced through the parked tile's LDS rows, not by DPP per pass */
-#endif
-#ifndef PW_EPI_CP_R
-#define PW_EPI_CP_R 0
-#endif
+// BatchNorm partial sums are reduced through the parked tile's LDS rows, not by DPP per pass.
 template <int EPI_, int BM, int IO, bool PT = false>
 struct PwEpilogueFull {
     static constexpr bool YB = (IO & PW_IO_Y) != 0, RB = (IO & PW_IO_R) != 0, YF16 = (IO & PW_IO_F16) != 0;
@@ -340,8 +242,8 @@ struct PwEpilogueFull {
             if (use_r) {
 #pragma unroll
                 for (int pass = 0; pass < 16; ++pass) {
-                    if constexpr (RB) rpre[pass] = __builtin_amdgcn_raw_buffer_load_b64(rR, voR, pass * stepR, PW_EPI_CP_R);
-                    else rpre[pass] = __builtin_amdgcn_raw_buffer_load_b128(rR, voR, pass * stepR, PW_EPI_CP_R);
+                    if constexpr (RB) rpre[pass] = __builtin_amdgcn_raw_buffer_load_b64(rR, voR, pass * stepR, 0);
+                    else rpre[pass] = __builtin_amdgcn_raw_buffer_load_b128(rR, voR, pass * stepR, 0);
                 }
             }
         }
@@ -370,7 +272,6 @@ struct PwEpilogueFull {
                     ct[row * 128 + wn * 64 + j * 32 + col] = acc[i][j][r];
                 }
         __syncthreads();
-        float sv0[do_stats ? 16 : 1], sv1[do_stats ? 16 : 1];
         const float* crow = ct + (wave * 2 + half) * 128 + col * 4;
 #pragma unroll
         for (int pass = 0; pass < 16; ++pass) {
@@ -408,67 +309,51 @@ struct PwEpilogueFull {
                 }
                 v[e] = x;
             }
-            if constexpr (!(PW_ABLATE & 4)) {
-                if constexpr (YB) {
-                    // (PT: the pitch keeps a straddling lane's 8 bytes inside the row; columns past T are padding)
-                    if (!PT || tcol < p.T) {
-                        const epi_u32x2 o2 = {pack16<YF16>(v[0], v[1]), pack16<YF16>(v[2], v[3])};
-                        __builtin_amdgcn_raw_buffer_store_b64(o2, rY, voY, pass * stepY, PW_EPI_CP_Y);
-                    }
-                } else if (PT && tcol + 3 >= p.T) {
-                    float* yq = reinterpret_cast<float*>(reinterpret_cast<char*>(p.Y) + (size_t)pass * stepY + (unsigned)voY);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (tcol + e < p.T) yq[e] = v[e];
-                } else {
-                    // NOT a buffer store: `buffer_store_dwordx4 v[96:99], v65, s[0:3], s4 offen` directly followed by a VALU write of
-                    // v99 stored the NEW v99 on gfx950 (sporadic wrong 4th elements) -- hipcc's hazard recognizer assumes that a
-                    // > 64-bit MUBUF store with an SGPR soffset needs no wait states before its data registers are overwritten.
-                    // For FLAT / global stores it pads.
-                    f32x4u* yq = reinterpret_cast<f32x4u*>(reinterpret_cast<char*>(p.Y) + (size_t)pass * stepY + (unsigned)voY);
-                    if constexpr (PW_EPI_CP_Y != 0) __builtin_nontemporal_store((f32x4u)v, yq);
-                    else *yq = v;
+            if constexpr (YB) {
+                // (PT: the pitch keeps a straddling lane's 8 bytes inside the row; columns past T are padding)
+                if (!PT || tcol < p.T) {
+                    const epi_u32x2 o2 = {pack16<YF16>(v[0], v[1]), pack16<YF16>(v[2], v[3])};
+                    __builtin_amdgcn_raw_buffer_store_b64(o2, rY, voY, pass * stepY, 0);
                 }
+            } else if (PT && tcol + 3 >= p.T) {
+                float* yq = reinterpret_cast<float*>(reinterpret_cast<char*>(p.Y) + (size_t)pass * stepY + (unsigned)voY);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (tcol + e < p.T) yq[e] = v[e];
+            } else {
+                // NOT a buffer store: `buffer_store_dwordx4 v[96:99], v65, s[0:3], s4 offen` directly followed by a VALU write of
+                // v99 stored the NEW v99 on gfx950 (sporadic wrong 4th elements) -- hipcc's hazard recognizer assumes that a
+                // > 64-bit MUBUF store with an SGPR soffset needs no wait states before its data registers are overwritten.
+                // For FLAT / global stores it pads.
+                f32x4u* yq = reinterpret_cast<f32x4u*>(reinterpret_cast<char*>(p.Y) + (size_t)pass * stepY + (unsigned)voY);
+                *yq = v;
             }
             if constexpr (do_stats) {
-                if constexpr (PW_EPI_STATS_LDS) {
-                    // this lane's partial sums -> the (consumed) first two floats of its own slot in the row just read
-                    *reinterpret_cast<float2*>(const_cast<float*>(crow) + pass * RPP * 128) = make_float2(s0, s1);
-                } else {
-                    sv0[pass] = half_wave_sum_dpp(s0);
-                    sv1[pass] = half_wave_sum_dpp(s1);
-                }
+                // this lane's partial sums -> the (consumed) first two floats of its own slot in the row just read
+                *reinterpret_cast<float2*>(const_cast<float*>(crow) + pass * RPP * 128) = make_float2(s0, s1);
             }
         }
         if constexpr (do_stats) {
             const size_t part = (size_t)b * p.n_ttiles + tt;
             float* sp = p.stats + (part * p.M + mrow) * 2;
-            if constexpr (PW_EPI_STATS_LDS) {
-                // Row sums WITHOUT a cross-lane reduction per pass (14 DPP instructions a pass = 224 of a wave's ~800 epilogue
-                // instructions, and the epilogue is bound by VALU issue): the 32 lanes of a half-wave parked their partials in the
-                // half-wave's own 16 rows; now lane l sums 16 of the 32 partials of row (l & 15) -- a rotated start per row keeps
-                // the 16 rows' reads on 16 different bank groups --, the two halves meet with one exchange, lanes 0-15 store one
-                // row's statistics each.  Fixed order: deterministic.
-                const int c = col & 15, base = col & 16;
-                const float* rp = ct + (wave * 2 + half + c * RPP) * 128;
-                float t0 = 0.f, t1 = 0.f;
+            // Row sums WITHOUT a cross-lane reduction per pass (14 DPP instructions a pass = 224 of a wave's ~800 epilogue
+            // instructions, and the epilogue is bound by VALU issue): the 32 lanes of a half-wave parked their partials in the
+            // half-wave's own 16 rows; now lane l sums 16 of the 32 partials of row (l & 15) -- a rotated start per row keeps
+            // the 16 rows' reads on 16 different bank groups --, the two halves meet with one exchange, lanes 0-15 store one
+            // row's statistics each.  Fixed order: deterministic.
+            const int c = col & 15, base = col & 16;
+            const float* rp = ct + (wave * 2 + half + c * RPP) * 128;
+            float t0 = 0.f, t1 = 0.f;
 #pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float2 v2 = *reinterpret_cast<const float2*>(rp + (base + ((i + c) & 15)) * 4);
-                    t0 += v2.x; t1 += v2.y;
-                }
-                t0 += __shfl_xor(t0, 16, 64);
-                t1 += __shfl_xor(t1, 16, 64);
-                if (col < 16) {
-                    const epi_u32x2 o2 = {__builtin_bit_cast(unsigned, t0), __builtin_bit_cast(unsigned, t1)};
-                    *reinterpret_cast<epi_u32x2*>(sp + c * RPP * 2) = o2;
-                }
-            } else if (col == 31) {
-#pragma unroll
-                for (int pass = 0; pass < 16; ++pass) {
-                    const epi_u32x2 o2 = {__builtin_bit_cast(unsigned, sv0[pass]), __builtin_bit_cast(unsigned, sv1[pass])};
-                    *reinterpret_cast<epi_u32x2*>(sp + pass * RPP * 2) = o2;
-                }
+            for (int i = 0; i < 16; ++i) {
+                const float2 v2 = *reinterpret_cast<const float2*>(rp + (base + ((i + c) & 15)) * 4);
+                t0 += v2.x; t1 += v2.y;
+            }
+            t0 += __shfl_xor(t0, 16, 64);
+            t1 += __shfl_xor(t1, 16, 64);
+            if (col < 16) {
+                const epi_u32x2 o2 = {__builtin_bit_cast(unsigned, t0), __builtin_bit_cast(unsigned, t1)};
+                *reinterpret_cast<epi_u32x2*>(sp + c * RPP * 2) = o2;
             }
         }
     }
@@ -476,11 +361,11 @@ struct PwEpilogueFull {
 
 // block-uniform: does the tile at (m0, t0) take the lean epilogue?
 __device__ __forceinline__ bool pw_tile_is_full(const PwParams& p, int BM, int m0, int t0) {
-    return PW_EPI_FAST != 0 && t0 + 128 <= p.T && m0 + BM <= p.M && p.bias == nullptr;
+    return t0 + 128 <= p.T && m0 + BM <= p.M && p.bias == nullptr;
 }
 // ... or at least in its rows (the last t-tile of a length that is not a multiple of 128)
 __device__ __forceinline__ bool pw_tile_rows_full(const PwParams& p, int BM, int m0) {
-    return PW_EPI_FAST >= 2 && m0 + BM <= p.M && p.bias == nullptr;
+    return m0 + BM <= p.M && p.bias == nullptr;
 }
 
 // Epilogue through LDS: the 128x128 fp32 accumulator tile is parked in the (now idle) 64 KB staging buffers,
@@ -570,7 +455,7 @@ __device__ __forceinline__ void pw_epilogue_lds(const PwParams& p, f32x16 (&acc)
             }
             v[e] = x;
         }
-        if (mv && !(PW_ABLATE & 4)) {
+        if (mv) {
             if constexpr (YB) {
                 // 4 bf16 = one 8-byte store; the pitch keeps it aligned, columns past T inside the pitch are padding
                 if (t < p.T) {
