@@ -6,20 +6,14 @@
 #include "common.h"
 #include "../../include/voice100_hip.h"
 #include "depthwise_common.h"   // DwFin: BatchNorm finalisation inside the depthwise kernels
-#ifndef IR_FUSE_BN3
-#define IR_FUSE_BN3 2      /* 1: reduce + finalise in one kernel; 2: ... + the affine, from registers */
-#endif
-// consumer-side BatchNorm finalisation in the depthwise kernels (DwPre): bit 0 forward (BatchNorm 1 from the expand GEMM's slab),
-// bit 1 backward (BatchNorm-2 backward from the project backward-data GEMM's slab).  Bit-identical results.  Round 2 measured it as
+// Consumer-side BatchNorm finalisation in the depthwise kernels (DwPre), with one group: forward BatchNorm 1 from the expand GEMM's slab,
+// backward BatchNorm-2 backward from the project backward-data GEMM's slab.  Bit-identical results.  Round 2 measured it as
 // a faster STEP (16 launches fewer) with a slower depthwise kernel and left it off because that kernel is the one graded against the
 // HBM roofline; the round-5 review asked for the default that minimises ms_per_step.  Round 6, with the finalisation's loads issued
 // ahead of the rows (dw_pre_issue) and the Toeplitz fragments built under their latency, A/B on one box (profiles/r06_dw_ab.txt):
 // 3.30 -> 3.24 ms/step, 151 -> 135 launches, glue 0.58 -> 0.51 ms; the depthwise forward pays +2 us a launch for it (0.189 -> 0.207 ms
 // per step, roofline.frac_nominal_step 0.57 -> 0.52: the fp64 finalisation of a channel sits in front of its first row), the fused
-// backward 0.388 -> 0.408.  On (3): the step is what counts; the slab bytes are counted in the kernels' algorithmic bytes.
-#ifndef IR_FUSE_PRE
-#define IR_FUSE_PRE 3
-#endif
+// backward 0.388 -> 0.408.  The step is what counts; the slab bytes are counted in the kernels' algorithmic bytes.
 
 namespace {
 struct Carver {
@@ -147,38 +141,30 @@ extern "C" int v100_ir_fwd_train(const int* sh, const void* const* P, void* stre
         void* y16 = (sh[IR_ACT16] >= 4 && (sh[IR_PREPPED] & 2)) ? const_cast<void*>(P[27]) : nullptr;
         if (x16) CK(v100_pw_gemm_io(w1bf, x16, nullptr, nullptr, nullptr, nullptr, 0, a1, nullptr, nullptr, nullptr, 1, st, B, hid, cin, T, PW_IO_X | PW_IO_Y, stream));
         else CK(v100_pw_gemm_io(w1bf, x, nullptr, nullptr, nullptr, nullptr, 0, a1, nullptr, nullptr, nullptr, 1, st, B, hid, cin, T, PW_IO_Y, stream));
-        const bool pre1 = (IR_FUSE_PRE & 1) && G == 1;      // ... and BatchNorm 1 too, from the expand GEMM's slab, before its first row
-        if (!pre1) CK(v100_bn_finalize_train(st, parts1, (long long)B * T, (const float*)P[2], (const float*)P[3], (float*)P[4], (float*)P[5], (long long*)P[6],
-                                             kMom, kEps, s1, t1, m1, r1, hid, stream));
-        if (G == 1) {          // the depthwise kernel finalises BatchNorm 2 itself (its workgroup owns the channel's sums)
+        if (G == 1) {          // the depthwise kernel finalises BatchNorm 2 itself (its workgroup owns the channel's sums) ...
             const DwFin fin{1, (double)B * T2, (const float*)P[8], (const float*)P[9], nullptr, s2, t2, nullptr, m2, r2,
                             (float*)P[10], (float*)P[11], (long long*)P[12], kMom, kEps};
-            DwPre pre{};
-            if (pre1) pre = DwPre{{1, (double)B * T, (const float*)P[2], (const float*)P[3], nullptr, s1, t1, nullptr, m1, r1,
-                                   (float*)P[4], (float*)P[5], (long long*)P[6], kMom, kEps}, st, parts1};
+            // ... and BatchNorm 1 too, from the expand GEMM's slab, before its first row
+            const DwPre pre{{1, (double)B * T, (const float*)P[2], (const float*)P[3], nullptr, s1, t1, nullptr, m1, r1,
+                             (float*)P[4], (float*)P[5], (long long*)P[6], kMom, kEps}, st, parts1};
             CK(dw_fwd_train_io_fin(a1, wd, s1, t1, a2, st, G, B, hid, T, K, DW_IO_X | DW_IO_Y, fin, pre, stream));
         } else {
+            CK(v100_bn_finalize_train(st, parts1, (long long)B * T, (const float*)P[2], (const float*)P[3], (float*)P[4], (float*)P[5], (long long*)P[6],
+                                      kMom, kEps, s1, t1, m1, r1, hid, stream));
             CK(v100_dwconv_fwd_train_io(a1, wd, s1, t1, a2, st, G, B, hid, T, K, DW_IO_X | DW_IO_Y, stream));
             CK(v100_bn_finalize_train(st, G, (long long)B * T2, (const float*)P[8], (const float*)P[9], (float*)P[10], (float*)P[11], (long long*)P[12],
                                       kMom, kEps, s2, t2, m2, r2, hid, stream));
         }
         const bool a316 = sh[IR_ACT16] >= 3;          // the project output (saved for backward) as bf16 too
         CK(v100_pw_gemm_io(w3bf, a2, nullptr, s2, t2, nullptr, 1, a3, nullptr, nullptr, nullptr, 1, st, B, cout, hid, T2, PW_IO_X | (a316 ? PW_IO_Y : 0), stream));
-        if (IR_FUSE_BN3) {     // BatchNorm 3 finalised by the block-output pass itself (one workgroup per channel)
-            const DwPre pre{{1, (double)B * T2, (const float*)P[14], (const float*)P[15], nullptr, s3, t3, nullptr, m3, r3,
-                             (float*)P[16], (float*)P[17], (long long*)P[18], kMom, kEps}, st, parts3};
-            // level 5: the residual comes from the bf16 shadow of x (what the expand GEMM above read), and an interior block of a stack
-            // (PREPPED bit 2: nothing reads its fp32 output) writes only the shadow of its own output
-            const bool r16 = sh[IR_ACT16] >= 5 && x16 && a316;            // (the previous block may not have written its fp32 output at all)
-            const bool noy = sh[IR_ACT16] >= 5 && y16 && a316 && (sh[IR_PREPPED] & 4);
-            CK(chan_affine2_fin(a3, res ? (r16 ? x16 : (const void*)x) : nullptr, noy ? nullptr : y, y16, B, cout, T2, a316 ? 1 : 0, pre, stream, r16 ? 1 : 0));
-            return V100_OK;
-        }
-        CK(v100_bn_finalize_train(st, parts3, (long long)B * T2, (const float*)P[14], (const float*)P[15], (float*)P[16], (float*)P[17], (long long*)P[18],
-                                  kMom, kEps, s3, t3, m3, r3, cout, stream));
-        if (y16) CK(v100_chan_affine2_shadow(a3, res ? x : nullptr, s3, t3, y, y16, B, cout, T2, a316 ? 1 : 0, stream));
-        else if (a316) CK(v100_chan_affine2_io(a3, res ? x : nullptr, s3, nullptr, t3, y, B, cout, T2, 1, stream));
-        else CK(v100_chan_affine2(a3, res ? x : nullptr, s3, nullptr, t3, y, B, cout, T2, stream));
+        // BatchNorm 3 finalised by the block-output pass itself (one workgroup per channel)
+        const DwPre pre{{1, (double)B * T2, (const float*)P[14], (const float*)P[15], nullptr, s3, t3, nullptr, m3, r3,
+                         (float*)P[16], (float*)P[17], (long long*)P[18], kMom, kEps}, st, parts3};
+        // level 5: the residual comes from the bf16 shadow of x (what the expand GEMM above read), and an interior block of a stack
+        // (PREPPED bit 2: nothing reads its fp32 output) writes only the shadow of its own output
+        const bool r16 = sh[IR_ACT16] >= 5 && x16 && a316;            // (the previous block may not have written its fp32 output at all)
+        const bool noy = sh[IR_ACT16] >= 5 && y16 && a316 && (sh[IR_PREPPED] & 4);
+        CK(chan_affine2_fin(a3, res ? (r16 ? x16 : (const void*)x) : nullptr, noy ? nullptr : y, y16, B, cout, T2, a316 ? 1 : 0, pre, stream, r16 ? 1 : 0));
         return V100_OK;
     }
     CK(v100_pw_gemm(w1, w1bf, x, nullptr, nullptr, nullptr, nullptr, 0, a1, nullptr, nullptr, nullptr, nullptr, 1, st, B, hid, cin, T, bf, stream));
@@ -189,7 +175,7 @@ extern "C" int v100_ir_fwd_train(const int* sh, const void* const* P, void* stre
     // a block that itself keeps fp32 storage (the stride-2 first layer) still emits the shadow its successor reads: the caller
     // passes P[27] only in bf16 precision at act16 level 4 (26 / 27 are not read otherwise) -- and, like the 16-bit blocks, lets that
     // pass finalise BatchNorm 3 itself (one launch fewer per step)
-    if (IR_FUSE_BN3 && !frozen && bf == 1 && (sh[IR_PREPPED] & 2) && P[27]) {
+    if (!frozen && bf == 1 && (sh[IR_PREPPED] & 2) && P[27]) {
         const DwPre pre{{1, (double)B * T2, (const float*)P[14], (const float*)P[15], nullptr, s3, t3, nullptr, m3, r3,
                          (float*)P[16], (float*)P[17], (long long*)P[18], kMom, kEps}, st, parts3};
         CK(chan_affine2_fin(a3, res ? x : nullptr, y, const_cast<void*>(P[27]), B, cout, T2, 0, pre, stream, 0));
@@ -269,18 +255,17 @@ extern "C" int v100_ir_bwd(const int* sh, const void* const* P, void* stream) {
     const int Gr = v100_dw_num_groups(B, cout);
     const bool a316 = sh[IR_ACT16] >= 3;              // a3 (saved) and da3 (workspace) stored as bf16
     bool da3_done = false;
-    if (a316 && IR_FUSE_BN3) {     // one workgroup per channel sums (dy, dy * a3) and finalises BatchNorm 3's backward itself ...
+    if (a316) {     // one workgroup per channel sums (dy, dy * a3) and finalises BatchNorm 3's backward itself ...
         const DwFin fin{2, (double)B * T2, g3, m3, r3, pp, qq, rr, (float*)P[20], (float*)P[21], nullptr, nullptr, nullptr, 0.f, 0.f};
         // ... and, when the channel's samples fit its registers, applies the affine to them in the same launch
-        if (IR_FUSE_BN3 >= 2 && chan_bn3_bwd(dy, a3, w.part, w.da3, B, cout, T2, fin, stream, dy16)) {
+        if (chan_bn3_bwd(dy, a3, w.part, w.da3, B, cout, T2, fin, stream, dy16)) {
             if ((rc = v100_launch_status()) != V100_OK) return rc;
             da3_done = true;
         } else if (dy16) return V100_ERR_SHAPE;           // (the stack executor asks for a 16-bit dy only where the one-pass kernel applies)
         else CK(chan_reduce2_io_fin(dy, a3, w.part, B, cout, T2, fin, stream));
     } else {
         if (dy16) return V100_ERR_SHAPE;
-        if (a316) CK(v100_chan_reduce2_io(dy, a3, w.part, Gr, B, cout, T2, 2, stream));
-        else CK(v100_chan_reduce2(dy, a3, w.part, Gr, B, cout, T2, stream));
+        CK(v100_chan_reduce2(dy, a3, w.part, Gr, B, cout, T2, stream));
         CK(bwd_finalize(w.part, Gr, (long long)B * T2, g3, m3, r3, pp, qq, rr, (float*)P[20], (float*)P[21], cout, stream));
     }
     if (da3_done) {}
@@ -296,16 +281,14 @@ extern "C" int v100_ir_bwd(const int* sh, const void* const* P, void* stream) {
                            PW_IO_R | (g16 ? PW_IO_Y : 0) | (a316 ? PW_IO_X : 0), stream));
         const int G16 = v100_dw_num_groups(B, hid);
         bool da1 = false;
-        const bool pre2 = (IR_FUSE_PRE & 2) && G16 == 1;    // BatchNorm-2 backward coefficients from the GEMM's slab, by the depthwise kernel
-        if (!pre2) CK(v100_bn_bwd_finalize(w.part, parts16, (long long)B * T2, g2, m2, r2, pp, qq, rr, (float*)P[17], (float*)P[18], hid, stream));
         if (G16 == 1) {        // BatchNorm-1 backward coefficients by the depthwise backward kernel itself
             // p / q / r are INPUTS of this kernel (BatchNorm-2 backward) and outputs of its finalisation (BatchNorm-1 backward):
             // the outputs go to the second coefficient set
             float *pp2 = w.pqr + 3 * mc, *qq2 = w.pqr + 4 * mc, *rr2 = w.pqr + 5 * mc;
             const DwFin fin{2, (double)B * T, g1, m1, r1, pp2, qq2, rr2, (float*)P[14], (float*)P[15], nullptr, nullptr, nullptr, 0.f, 0.f};
-            DwPre pre{};
-            if (pre2) pre = DwPre{{2, (double)B * T2, g2, m2, r2, pp, qq, rr, (float*)P[17], (float*)P[18], nullptr, nullptr, nullptr, 0.f, 0.f},
-                                  w.part, parts16};
+            // (BatchNorm-2 backward coefficients: from the GEMM's slab, by the depthwise kernel too)
+            const DwPre pre{{2, (double)B * T2, g2, m2, r2, pp, qq, rr, (float*)P[17], (float*)P[18], nullptr, nullptr, nullptr, 0.f, 0.f},
+                            w.part, parts16};
             // Round 5: where the streaming kernel can keep a wave's rows in registers (one group, B <= 32, every hidden tensor bf16) it
             // writes the FINISHED gradient da1 = p dz1 + q a1 + r (into the dz1 buffer) and the two consumers below read ONE plain
             // bf16 tensor -- bit for bit the operand their on-load transform of (dz1, a1) produced.
@@ -314,6 +297,7 @@ extern "C" int v100_ir_bwd(const int* sh, const void* const* P, void* stream) {
                              g16 ? (DW_IO_X | DW_IO_X2 | DW_IO_AUX | DW_IO_Y) : (DW_IO_X2 | DW_IO_AUX), fin, pre, stream, da1 ? 1 : 0));
             pp = pp2; qq = qq2; rr = rr2;
         } else {
+            CK(v100_bn_bwd_finalize(w.part, parts16, (long long)B * T2, g2, m2, r2, pp, qq, rr, (float*)P[17], (float*)P[18], hid, stream));
             CK(v100_dwconv_bwd_io(w.dz2, a2, wd, pp, qq, rr, a1, s1, t1, w.dz1, w.part, w.slab, (float*)P[16], G16, B, hid, T, K,
                                   g16 ? (DW_IO_X | DW_IO_X2 | DW_IO_AUX | DW_IO_Y) : (DW_IO_X2 | DW_IO_AUX), stream));
             CK(v100_bn_bwd_finalize(w.part, G16, (long long)B * T, g1, m1, r1, pp, qq, rr, (float*)P[14], (float*)P[15], hid, stream));
@@ -686,7 +670,7 @@ extern "C" int v100_ir_stack_bwd(const int* desc, const void* const* params, con
     auto grad16_ok = [&](int i) {                          // block i can consume a 16-bit dy AND produce a 16-bit dx
         const int* sh = blk[i].sh;
         return grad16_on && desc[ST_LEVEL] >= 5 && sh[IR_ACT16] >= 3 && sh[IR_STRIDE] == 1 && sh[IR_T] >= 8 &&
-               IR_FUSE_BN3 >= 2 && chan_bn3_bwd_fits(sh[IR_B], sh[IR_T]) && v100_ir_act16_supported(sh) &&
+               chan_bn3_bwd_fits(sh[IR_B], sh[IR_T]) && v100_ir_act16_supported(sh) &&
                dw_bwd_da1_supported(sh[IR_B], sh[IR_HID], sh[IR_T], sh[IR_K], v100_dw_num_groups(sh[IR_B], sh[IR_HID])) && sh[IR_ACT16] >= 2;
     };
     bool dy_is16 = false;

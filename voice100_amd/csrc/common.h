@@ -64,9 +64,6 @@ __device__ __forceinline__ float wave_sum_dpp_hi(float v) {
     return v;
 }
 
-#ifndef PACK_BF16_ASM
-#define PACK_BF16_ASM 0
-#endif
 // fp32 -> bf16 round-to-nearest-even; plain cast keeps NaN a NaN (v_cvt_pk_bf16_f32 on gfx950)
 __device__ __forceinline__ u16 f2bf(float f) {
     __bf16 h = (__bf16)f;
@@ -75,16 +72,10 @@ __device__ __forceinline__ u16 f2bf(float f) {
 __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
     // one v_cvt_pk_bf16_f32 (RNE, NaN-preserving).  As a VECTOR conversion, not inline asm: hipcc emits the same instruction, can
     // schedule it, and pads the MFMA-result -> VALU-read hazard that it does not see through an asm statement
-#if PACK_BF16_ASM
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-#else
     typedef __bf16 pk_bf16x2 __attribute__((ext_vector_type(2)));
     typedef float pk_f32x2 __attribute__((ext_vector_type(2)));
     const pk_f32x2 f = {lo, hi};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f, pk_bf16x2));
-#endif
 }
 
 // 16-bit operand formats of the MFMA GEMMs: bf16 (training + inference) or IEEE fp16 (inference), fp32 accumulate
@@ -119,10 +110,7 @@ static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 // traffic on the depthwise launches of those steps and 8-10 % of their time (profiles/r06_dw_ab.txt: T = 568 -> 51.4 %, 576 -> 55.4 % of
 // 8 TB/s).  A tensor of ONE row per channel (B == 1: the channel-major inference matrices [C][B P], which the GEMMs see as B = 1,
 // T = B P) keeps the 8-sample rule: its row length is the caller's column count and must not be re-padded.
-#ifndef V100_PITCH_LINES
-#define V100_PITCH_LINES 1     /* 0: the rounds 2-5 rule, (T + 7) & ~7 everywhere (A/B builds) */
-#endif
 __host__ __device__ __forceinline__ int v100_pitch16(int T, int B) {
-    return (V100_PITCH_LINES && B > 1 && T >= 256) ? ((T + 63) & ~63) : ((T + 7) & ~7);
+    return (B > 1 && T >= 256) ? ((T + 63) & ~63) : ((T + 7) & ~7);
 }
 // (exported to the host side as v100_row_pitch16, block.hip)

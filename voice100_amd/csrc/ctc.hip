@@ -9,13 +9,9 @@
 // (log_softmax's backward is the identity here because that expression sums to zero over c) is formed by one
 // wave per frame with LDS float atomics into the <= 128 class bins.
 #include "common.h"
-#include <cstdlib>
 #include <math.h>
 #include <type_traits>
 
-#ifndef CTC_SKEW
-#define CTC_SKEW 1
-#endif
 #define CTC_CHUNK 64
 #define CTC_MAXV 128
 #define NEG_INF (-INFINITY)
@@ -47,8 +43,8 @@ __global__ void ctc_lse_kernel(const float* __restrict__ logits, float* __restri
 }
 
 // grid (B, 2): y = 0 alpha, y = 1 beta.  lattice[b][t][s] written for t < in_len[b], s < 2*tgt_len[b]+1.
-// NS = lattice states per thread: 256 * NS >= 2 * Lmax + 1 (NS = 2 covers transcripts of up to 255 tokens, the
-// benchmark's; 4 / 8 / 16 cover up to 511 / 1023 / 2047 -- nn.CTCLoss itself has no limit, asr.py:105).
+// NS = lattice states per thread: 256 * NS >= 2 * Lmax + 1 (8 / 16 cover transcripts of up to 1023 / 2047 tokens -- nn.CTCLoss itself
+// has no limit, asr.py:105; up to 1024 states, i.e. 511 tokens, take ctc_lattice_skew_kernel below).
 template <int NS>
 __global__ __launch_bounds__(256) void ctc_lattice_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
                                                           const long long* __restrict__ targets, const int* __restrict__ in_len,
@@ -139,17 +135,13 @@ __global__ __launch_bounds__(256) void ctc_lattice_kernel(const float* __restric
 // go through LDS, into a ring slot per frame, and the waves run SKEWED: wave w may start frame q as soon as wave w-1 has
 // published frame q-1 (a progress word per wave; no workgroup barrier in the recursion).  Emission log-probabilities are
 // gathered straight from global memory eight frames ahead.
-// (Round 5, measured at B = 32, T' = 512, 100-token targets, whole head 134 us: timing-only ablations (CTC_ABL) put 62 us on the
+// (Round 5, measured at B = 32, T' = 512, 100-token targets, whole head 134 us: timing-only ablations put 62 us on the
 //  handshake, 37 us on the four transcendentals per frame, 10-12 us each on the lattice store and the emission gathers; the same
 //  pipeline in LOCKSTEP -- fixed skew of two frames, one s_barrier per frame, no progress words -- was built and measured SLOWER,
 //  143 us: a four-wave s_barrier costs more per frame (~75 ns) than the polling it replaces.  DESIGN.md section 8.)
 // log2-domain log-sum-exp of three terms on the raw v_exp_f32 / v_log_f32 (no range scaling: the sum lies in [1, 3] or is exactly
 // 0), branch-free: an all -inf input gives mm + log2(0) = -inf, never inf - inf
-#ifndef CTC_ABL
-#define CTC_ABL 0      /* timing-only ablations (wrong results): 1 no lattice store, 2 no transcendentals, 4 no handshake, 8 no emission loads */
-#endif
 __device__ __forceinline__ float ctc_lse3_log2(float a, float b, float c) {
-    if constexpr (CTC_ABL & 2) return (a + b + c) * 0.3f;
     const float mm = fmaxf(fmaxf(fmaxf(a, b), c), -1e30f);
     const float sum = __builtin_amdgcn_exp2f(a - mm) + __builtin_amdgcn_exp2f(b - mm) + __builtin_amdgcn_exp2f(c - mm);
     return mm + __builtin_amdgcn_logf(sum);
@@ -201,7 +193,6 @@ __global__ __launch_bounds__(1024) void ctc_lattice_skew_kernel(const float* __r
     auto emission = [&](int q) -> float {
         const int qq = q < Tb ? q : Tb - 1;
         const int t = dir == 0 ? qq : Tb - 1 - qq;
-        if constexpr (CTC_ABL & 8) return -3.f - 0.001f * (float)t;
         return (lg[(size_t)t * V] - ls[t]) * 1.44269504088896340736f;       // log2 units: the recursion runs on exp2 / log2 directly
     };
     float cur[CTC_PF], nxt[CTC_PF];
@@ -272,7 +263,7 @@ __global__ __launch_bounds__(1024) void ctc_lattice_skew_kernel(const float* __r
         asm volatile("" ::: "memory");       // program order only: LDS performs one wave's writes in the order they were issued
         if (lane == 0) __hip_atomic_store(&progress[w], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         a_prev = v;
-        if (!(CTC_ABL & 1)) if (active) *lrow = v * 0.69314718055994530942f;      // the lattice is stored in natural-log units
+        if (active) *lrow = v * 0.69314718055994530942f;      // the lattice is stored in natural-log units
         lrow += lstep;
     };
     auto run = [&](auto up_t, auto down_t) {
@@ -296,7 +287,7 @@ __global__ __launch_bounds__(1024) void ctc_lattice_skew_kernel(const float* __r
             for (int j = 0; j < CTC_PF; ++j) cur[j] = nxt[j];
         }
     };
-    const bool has_up = !(CTC_ABL & 4) && w > 0, has_down = !(CTC_ABL & 4) && w < NW - 1;
+    const bool has_up = w > 0, has_down = w < NW - 1;
     if (has_up && has_down) run(std::true_type{}, std::true_type{});
     else if (has_up) run(std::true_type{}, std::false_type{});
     else if (has_down) run(std::false_type{}, std::true_type{});
@@ -463,19 +454,14 @@ static int ctc_run(const float* logits, const long long* targets, const int* in_
         (void)hipFuncSetAttribute((const void*)ctc_lattice_kernel<NS_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);       \
     V100_GGL(ctc_lattice_kernel<NS_>, dim3(B, 2), dim3(256), shmem, st, logits, lse, targets, in_len, tgt_len, alpha, beta, \
                        nll, T, V, Lmax, Smax, blank)
-    if (CTC_SKEW && Smax <= 1024) {
+    if (Smax <= 1024) {
         const int nw = (Smax + 63) / 64;
         V100_GGL(ctc_lattice_skew_kernel, dim3(B, 2), dim3(64 * nw), 0, st, logits, lse, targets, in_len, tgt_len, alpha, beta,
                            nll, T, V, Lmax, Smax, blank, stall);
-    } else if (Smax <= 512) { CTC_LATTICE(2); }
-    else if (Smax <= 1024) { CTC_LATTICE(4); }
-    else if (Smax <= 2048) { CTC_LATTICE(8); }
+    } else if (Smax <= 2048) { CTC_LATTICE(8); }
     else { CTC_LATTICE(16); }
 #undef CTC_LATTICE
-    static const int bvt_nw = [] { const char* e = getenv("V100_CTC_BVT_NW"); return e ? atoi(e) : 16; }();      // A/B: frames per workgroup of the [B, V, T] form
-    if (grad_bvt && bvt_nw == 4) V100_GGL((ctc_grad_kernel<4, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, logits, lse, targets, in_len, tgt_len,
-                           alpha, beta, nll, grad, B, T, V, Lmax, Smax, blank, loss ? 1 : 0, stall, loss);
-    else if (grad_bvt) V100_GGL((ctc_grad_kernel<16, true>), dim3((unsigned)((rows + 15) / 16)), dim3(1024), 0, st, logits, lse, targets, in_len, tgt_len,
+    if (grad_bvt) V100_GGL((ctc_grad_kernel<16, true>), dim3((unsigned)((rows + 15) / 16)), dim3(1024), 0, st, logits, lse, targets, in_len, tgt_len,
                            alpha, beta, nll, grad, B, T, V, Lmax, Smax, blank, loss ? 1 : 0, stall, loss);
     else V100_GGL((ctc_grad_kernel<4, false>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, logits, lse, targets, in_len, tgt_len,
                   alpha, beta, nll, grad, B, T, V, Lmax, Smax, blank, loss ? 1 : 0, stall, loss);     // (the 'mean' reduction rides in block 0)

@@ -151,7 +151,13 @@ __device__ __forceinline__ void dw_finalize_parts(const DwPre& pre, int C, int c
 // blockIdx -> channel for kernels that run ONE workgroup per channel over [B][C][T] rows: workgroups are dealt to the 8 XCDs round-robin;
 // groups of GR consecutive channels go to one XCD (the groups round-robin), so an XCD sweeps GR-row runs of every utterance and the
 // channels that share a 128-byte line of a per-channel array ([parts][C][2] slabs, BatchNorm parameters) share an L2.  Identity when
-// C is not a multiple of 8 GR.  (Round 6: depthwise_stream16.h dws_chan, measured there; bn.hip's block-boundary passes.)
+// C is not a multiple of 8 GR.  Used with GR = 16 by the streaming depthwise kernels and bn.hip's block-boundary passes: the 16 channels
+// whose partial sums share one 128-byte line of a producer's slab then run on ONE XCD, back to back, so the consumer-side finalisation
+// (dw_pre_issue) fetches each slab line into one L2 once instead of into all eight (measured: +9 / +18 MB of reads per 1024- / 2048-channel
+// launch, 1.14 x the algorithmic bytes).  Round 6, 8 layers on a rotating working set: forward 177 -> 170 us, plain fused backward
+// 326 -> 301, kept-rows form 366 -> 340 -- the remap pays without any finalisation in the kernel too: an XCD's 32 CUs sweep 16 KB runs
+// of each utterance instead of every eighth 1 KB row; HBM bytes of the forward launches 1.132 -> 1.018 x algorithmic with the
+// finalisation on.  bn.hip's passes: step 3.218 -> 3.208 ms, A/B on one box.
 template <int GR>
 __device__ __forceinline__ int v100_chan_of_block(int bid, int C) {
     if (C & (8 * GR - 1)) return bid;
@@ -162,7 +168,7 @@ __device__ __forceinline__ int v100_chan_of_block(int bid, int C) {
 // dw_finalize_parts with its loads issued AHEAD (streaming depthwise kernels, round 6).  Inside the kernel the finalisation used to sit
 // behind the row requests: its slab reads and per-channel parameter reads were YOUNGER than the wave's first rows, vmcnt retires in
 // order, so wave 0 waited a full HBM round trip for rows it did not need yet and three waves waited for wave 0 at the barrier
-// (IR_FUSE_PRE cost the forward kernel 10 %).  dw_pre_issue requests everything at kernel entry, in front of the rows, with no branch
+// (round 2: it cost the forward kernel 10 %).  dw_pre_issue requests everything at kernel entry, in front of the rows, with no branch
 // (inactive waves / modes load through an out-of-range buffer offset -- no bytes move -- or from a harmless valid address);
 // dw_pre_finish is pure arithmetic on those registers: same values, same order of summation as dw_finalize_parts (parts past the slab
 // read as 0.0 and add nothing), so the coefficients are bit-identical.  Up to DW_PRE_MAXPARTS partial sums (4 per lane).
@@ -533,14 +539,12 @@ __global__ __launch_bounds__(256) void dwconv_kernel(DwParams p) {
 // Stride-1 layers with a specialised kernel size run on the Toeplitz-MFMA kernels (round 3: the register-window VALU kernels they
 // replaced are no longer instantiated for those sizes -- they remain for the stride-2 opener and, as dwconv_generic_kernel, for
 // everything else).  Precision knob, read once: V100_DW_DIGITS = 2 | 3 bf16 digits per fp32 tap / sample (default 3: fp32-exact
-// products).  With 16-bit activation storage the taps default to DW_DIGITS16 (below).
+// products).
 // Round 6: with 16-bit activation storage the taps are ONE digit by default -- rounded to bf16 (fp16 at precision "fp16") like the data
 // operand, which is what F.conv1d computes under the reference's 16-bit autocast (its weights are cast with its input); the second
 // digit bought nothing the rounded data could show and cost a second pass over the matrix pipe per Toeplitz block (step -0.9 %, the
 // depthwise family +0.02 of 8 TB/s, and power: profiles/r06_dw_digits_ab.txt).  V100_DW_DIGITS=3 restores fp32-exact taps.
-#ifndef DW_DIGITS16
-#define DW_DIGITS16 1
-#endif
+constexpr int DW_DIGITS16 = 1;
 struct DwPathConfig { int digits; bool digits3; };
 static inline DwPathConfig dw_path_config() {
     static const DwPathConfig cfg = [] {
@@ -558,9 +562,6 @@ static inline DwPathConfig dw_path_config() {
 
 // One launcher per (input mode, output mode) pair, each in its own translation unit (they compile
 // in parallel).  Returns false when (K, stride) has no specialisation.
-#ifndef DW_FUSED_R
-#define DW_FUSED_R 4
-#endif
 template <int IM, int OM, bool WG = false, int IO = 0>
 static bool dw_launch_specialised(const DwParams& p, hipStream_t st, const V100TimedLaunch& tl) {
     dim3 grid(p.C, p.G);
@@ -584,7 +585,7 @@ static bool dw_launch_specialised(const DwParams& p, hipStream_t st, const V100T
     }
     if constexpr (IO != 0) return false;      // 16-bit storage exists on the MFMA kernels only
     else {
-    const bool big = p.Tout > 256 && !(WG && DW_FUSED_R == 4);
+    const bool big = p.Tout > 256 && !WG;
     // rows of any length take the 16-byte (dword-aligned) global path; tails are masked per element
 #define DW_GO(KK, SS)                                                                                             \
     do {                                                                                                          \

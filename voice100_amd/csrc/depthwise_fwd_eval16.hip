@@ -4,13 +4,6 @@
 #include "depthwise_common.h"
 #include "depthwise_stream16.h"
 
-#ifndef DWS_DEPTH
-#define DWS_DEPTH 1
-#endif
-#ifndef DWS_NT
-#define DWS_NT 1
-#endif
-
 // f16: the tensors hold fp16 (streaming kernel only: rows of up to 768 outputs); p.cm: channel-major storage (streaming kernel only)
 bool dw_launch_fwd_eval16(const DwParams& p, hipStream_t st, const V100TimedLaunch& tl, bool f16) {
     if (f16) {
@@ -19,8 +12,8 @@ bool dw_launch_fwd_eval16(const DwParams& p, hipStream_t st, const V100TimedLaun
         // two fp16 digits per tap: 22 mantissa bits, far below the fp16 rounding of the stored activations
 #define X(KK)                                                                                                                           \
     if (p.K == KK) {                                                                                                                    \
-        if (p.Tin <= 512) V100_LAUNCH(tl, (dwconv_fwd16_stream_kernel<KK, DW_DIGITS16, DWS_DEPTH, DWS_NT * 2, 2, true, true>), grid, dim3(256), 0, st, p);  \
-        else V100_LAUNCH(tl, (dwconv_fwd16_stream_kernel<KK, DW_DIGITS16, DWS_DEPTH, DWS_NT * 2, 3, true, true>), grid, dim3(256), 0, st, p);         \
+        if (p.Tin <= 512) V100_LAUNCH(tl, (dwconv_fwd16_stream_kernel<KK, DW_DIGITS16, DWS_DEPTH, DWS_CP, 2, true, true>), grid, dim3(256), 0, st, p);  \
+        else V100_LAUNCH(tl, (dwconv_fwd16_stream_kernel<KK, DW_DIGITS16, DWS_DEPTH, DWS_CP, 3, true, true>), grid, dim3(256), 0, st, p);         \
         return true;                                                                                                                    \
     }
         V100_DW_SPECIALISED(X)
@@ -32,8 +25,8 @@ bool dw_launch_fwd_eval16(const DwParams& p, hipStream_t st, const V100TimedLaun
         dim3 grid(p.C, p.G);
 #define GO(KK, NTT)                                                                                                                     \
     do {                                                                                                                                \
-        if (p.Tin <= 512) V100_LAUNCH(tl, (dwconv_fwd16_stream_kernel<KK, NTT, DWS_DEPTH, DWS_NT * 2, 2, true>), grid, dim3(256), 0, st, p);  \
-        else V100_LAUNCH(tl, (dwconv_fwd16_stream_kernel<KK, NTT, DWS_DEPTH, DWS_NT * 2, 3, true>), grid, dim3(256), 0, st, p);         \
+        if (p.Tin <= 512) V100_LAUNCH(tl, (dwconv_fwd16_stream_kernel<KK, NTT, DWS_DEPTH, DWS_CP, 2, true>), grid, dim3(256), 0, st, p);  \
+        else V100_LAUNCH(tl, (dwconv_fwd16_stream_kernel<KK, NTT, DWS_DEPTH, DWS_CP, 3, true>), grid, dim3(256), 0, st, p);         \
     } while (0)
 #define X(KK)                                                                                                                           \
     if (p.K == KK) {                                                                                                                    \

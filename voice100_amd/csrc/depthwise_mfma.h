@@ -40,9 +40,7 @@ typedef short dwm_s16x4 __attribute__((ext_vector_type(4)));
 // Row stride (floats) of the E tiles' exchange buffer.  Thread jf sums the diagonal E[r + jf + off][r]: with 16-float rows the lanes of a
 // ds_read_b32 sit 16 dwords apart -- two banks for 32 lanes, a 16-way conflict on every one of the 64 reads per thread (round 6: this
 // was most of the fused backward's 39-49 % SQ_LDS_BANK_CONFLICT) -- with 17 they walk the banks.
-#ifndef DWM_EP
-#define DWM_EP 17
-#endif
+constexpr int DWM_EP = 17;
 
 // 8 bf16 of one MFMA operand fragment as two transposing LDS reads (rows 4G..4G+3 and 16+4G..16+4G+3 of a [32 x 16] tile,
 // G = lane >> 4, column lane & 15); `tile` points at element 0 of the tile, 8-byte aligned.  EXEC must be all ones.
@@ -140,29 +138,21 @@ __device__ __forceinline__ float dwm_elem8(const dwm_u32x4& r, int e) {      // 
     const unsigned w = r[e >> 1];
     return __builtin_bit_cast(float, (e & 1) ? (w & 0xffff0000u) : (w << 16));
 }
-// DWM_CP: cache policy of the bf16-stored row streams of the act16 kernels (2 = nontemporal; in-step A/B of the general kernel: +-0, profiles/r03_ab_misc.txt; the streaming kernels take theirs as a template argument;
-// +16 % on the rotating-working-set micro-benchmark of the streaming kernels, profiles/r03_dw_stream_ab.txt)
-#ifndef DWM_CP
-#define DWM_CP 0
-#endif
-template <int CP = 0>
+// (nontemporal row streams in this general kernel: +-0 in the step, profiles/r03_ab_misc.txt; the streaming kernels take theirs as a
+// template argument)
 __device__ __forceinline__ dwm_u32x4 dwm_load_run8(__amdgpu_buffer_rsrc_t r, int voff_elems, unsigned row_elems) {
-    return __builtin_amdgcn_raw_buffer_load_b128(r, voff_elems < 0x20000000 ? voff_elems * 2 : 0x7ffffff0, (int)(row_elems * 2u), CP);
+    return __builtin_amdgcn_raw_buffer_load_b128(r, voff_elems < 0x20000000 ? voff_elems * 2 : 0x7ffffff0, (int)(row_elems * 2u), 0);
 }
 template <bool B16>
 struct DwmRun { typedef f32x4 type; };
 template <>
 struct DwmRun<true> { typedef dwm_u32x2 type; };
-template <bool B16, int CP = 0>
+template <bool B16>
 __device__ __forceinline__ typename DwmRun<B16>::type dwm_load_run(__amdgpu_buffer_rsrc_t r, int voff_elems, unsigned row_elems) {
     // voff_elems: element offset inside the row, or a huge value for "out of range" (hardware returns zero)
-    if constexpr (B16) return __builtin_amdgcn_raw_buffer_load_b64(r, voff_elems < 0x20000000 ? voff_elems * 2 : 0x7ffffff0, (int)(row_elems * 2u), CP);
+    if constexpr (B16) return __builtin_amdgcn_raw_buffer_load_b64(r, voff_elems < 0x20000000 ? voff_elems * 2 : 0x7ffffff0, (int)(row_elems * 2u), 0);
     else return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff_elems < 0x20000000 ? voff_elems * 4 : 0x7ffffff0, (int)(row_elems * 4u), 0));
 }
-
-#ifndef DWM_SINGLE
-#define DWM_SINGLE 1
-#endif
 
 template <int K, int IM, int OM, int NT, bool WG = false, int IO = 0>
 __global__ __launch_bounds__(256, WG ? 3 : 4) void dwconv_mfma_kernel(DwParams p) {
@@ -279,7 +269,7 @@ __global__ __launch_bounds__(256, WG ? 3 : 4) void dwconv_mfma_kernel(DwParams p
         // being re-derived from out-of-range loads on every row (half the staging instructions, no bounds selects).
         // Forward only: A/B on one box, 9-layer totals -- forward 167.4 -> 160.0 us, the fused backward (two input streams, xin images;
         // its own staging is not what bounds it) 347-358 -> 354-372 us.
-        const bool single = DWM_SINGLE && W8 && !WG && ntiles == 1 && Tin <= TILE && (Tin & 7) == 0;        // kernel-uniform
+        const bool single = W8 && !WG && ntiles == 1 && Tin <= TILE && (Tin & 7) == 0;        // kernel-uniform
         const int lpad = -in0a;
         if constexpr (W8) {
             if (single) {
@@ -298,8 +288,8 @@ __global__ __launch_bounds__(256, WG ? 3 : 4) void dwconv_mfma_kernel(DwParams p
 #pragma unroll
             for (int v = 0; v < NVL; ++v) {
                 if constexpr (W8) {
-                    raw8[v] = dwm_load_run8<DWM_CP>(rx, vo[v], row * (unsigned)PinX);
-                    if constexpr (TWO) raw8b[v] = dwm_load_run8<DWM_CP>(rx2, vo[v], row * (unsigned)PinX2);
+                    raw8[v] = dwm_load_run8(rx, vo[v], row * (unsigned)PinX);
+                    if constexpr (TWO) raw8b[v] = dwm_load_run8(rx2, vo[v], row * (unsigned)PinX2);
                 } else {
                     rawx[v] = dwm_load_run<XB>(rx, vo[v], row * (unsigned)PinX);
                     if constexpr (TWO) rawx2[v] = dwm_load_run<X2B>(rx2, vo[v], row * (unsigned)PinX2);
@@ -316,7 +306,7 @@ __global__ __launch_bounds__(256, WG ? 3 : 4) void dwconv_mfma_kernel(DwParams p
                 for (int sub = 0; sub < SUBS; ++sub) {
                     const int t0 = out0 + 256 * sub + 16 * n_ + 4 * q_;
                     if constexpr (AUXB) {
-                        const dwm_u32x2 a2 = dwm_load_run<true, W8 ? DWM_CP : 0>(raux, t0 < Tout ? t0 : 0x7ffffff0, (unsigned)(b * p.C + c) * (unsigned)PoutA);
+                        const dwm_u32x2 a2 = dwm_load_run<true>(raux, t0 < Tout ? t0 : 0x7ffffff0, (unsigned)(b * p.C + c) * (unsigned)PoutA);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) auxv[sub][r] = (t0 + r < Tout) ? dwm_elem(a2, r) : 0.f;
                     } else {
@@ -470,8 +460,7 @@ __global__ __launch_bounds__(256, WG ? 3 : 4) void dwconv_mfma_kernel(DwParams p
                     if (t0 < Tout) {
                         const dwm_u32x2 o2 = {dwm_pack_rne(outv[0], outv[1]), dwm_pack_rne(outv[2], outv[3])};
                         dwm_u32x2* yq = reinterpret_cast<dwm_u32x2*>(reinterpret_cast<unsigned short*>(p.y) + ((size_t)b * p.C + c) * PoutY + t0);
-                        if constexpr (W8 && DWM_CP != 0) __builtin_nontemporal_store(o2, yq);
-                        else *yq = o2;
+                        *yq = o2;
                     }
                 } else if (t0 + 3 < Tout) {
                     const f32x4 o = {outv[0], outv[1], outv[2], outv[3]};

@@ -30,66 +30,28 @@
 // instead of two tiles (same values, a different order of the fp32 partial sums).
 #pragma once
 
-// Round-6 knobs of the streaming kernels (A/B builds: tools/ab_variants.sh; the defaults are what ships)
-#ifndef DWS_XSWZ
-#define DWS_XSWZ 1            /* xin image of the fused backward stored with an XOR swizzle of its 8-byte chunks (see dws_xoff) */
-#endif
-#ifndef DWS_TAIL
-#define DWS_TAIL 1            /* DA1: finish BatchNorm 1's backward and store the kept rows BEFORE the weight-gradient tiles go through LDS */
-#endif
-#ifndef DWS_XCD
-#define DWS_XCD 2             /* blockIdx -> channel: 0 identity, 1 C/8 consecutive channels per XCD, 2 groups of DWS_XCD_GROUP channels per XCD */
-#endif
-#ifndef DWS_XCD_GROUP
-#define DWS_XCD_GROUP 16      /* a power of two */
-#endif
-
-// blockIdx.x -> channel.  Workgroups are dealt to the 8 XCDs round-robin; with DWS_XCD the channels c, c + 1, ... (adjacent 1 KB rows
-// of every utterance) go to the same XCD: rows whose pitch is not a whole number of 128-byte lines then share their boundary lines in
-// ONE L2 instead of fetching them twice.
-__device__ __forceinline__ int dws_chan(int bid, int C) {
-#if DWS_XCD == 1
-    return (C & 7) == 0 ? (bid & 7) * (C >> 3) + (bid >> 3) : bid;
-#elif DWS_XCD == 2
-    // groups of 16 consecutive channels per XCD, the groups dealt round-robin: the 16 channels whose partial sums share one 128-byte
-    // line of a producer's slab [parts][C][2] (and whose BatchNorm parameters share a line) then run on ONE XCD, back to back, so the
-    // consumer-side finalisation (dw_pre_issue) fetches each slab line into one L2 once instead of into all eight (measured: +9 / +18 MB
-    // of reads per 1024- / 2048-channel launch, 1.14 x the algorithmic bytes)
-    // (round 6, 8 layers on a rotating working set: forward 177 -> 170 us, plain fused backward 326 -> 301, kept-rows form 366 -> 340 --
-    // the remap pays without any finalisation in the kernel too: an XCD's 32 CUs sweep 16 KB runs of each utterance instead of every
-    // eighth 1 KB row; HBM bytes of the forward launches 1.132 -> 1.018 x algorithmic with the finalisation on)
-    constexpr int GR = DWS_XCD_GROUP;
-    if (C & (8 * GR - 1)) return bid;
-    const int xcd = bid & 7, idx = bid >> 3;
-    return ((idx / GR) * 8 + xcd) * GR + (idx & (GR - 1));
-#else
-    (void)C;
-    return bid;
-#endif
-}
+// Rows of loads in flight per wave beyond the current one, and the cache policy of the row traffic (profiles/r03_dw_stream_ab.txt: one
+// row with nontemporal traffic wins in every regime, in the 512- and the 768-position form, forward and plain fused backward; two rows
+// tie on a rotating working set and lose behind the producing GEMM; four lose everywhere)
+constexpr int DWS_DEPTH = 1;
+constexpr int DWS_CP = 2;             // nontemporal: the rows are read once and written once
+// ... in the kept-rows (DA1) form of the fused backward.  Round 6, 8 layers on a rotating working set (profiles/r06_dw_ab.txt):
+// 1 -> 2: 407 -> 366 us.  That form holds two workgroups per CU (its kept rows fill the register file), and unlike the plain form --
+// which a depth of 2 never helped -- it has too few bytes in flight at one row per wave; the extra row costs no occupancy here.
+constexpr int DWS_KEEP_DEPTH = 2;
 
 // Element offset, inside a 256-position half of the xin image, of the 4-sample chunk q of tile row n (row-major [16 x 16] bf16 tiles,
-// 32-byte rows).  Plain: 16 n + 4 q.  A ds_write_b64 is served in four groups of 16 consecutive lanes on 32 banks: with q fixed in a
+// 32-byte rows).  Plain would be 16 n + 4 q.  A ds_write_b64 is served in four groups of 16 consecutive lanes on 32 banks: with q fixed in a
 // group the plain addresses are 8 dwords apart -- 4 lanes per bank, a 4-way conflict on both stores of every row.  XOR-ing the chunk
 // index with bits 2..3 of the row spreads each group over all 32 banks; the transposing read supplies one address per (row, chunk), so
 // it simply asks for the swizzled chunk (dws_tr_fragment_x) and still covers 256 contiguous bytes per 32 lanes: conflict-free both ways.
-__device__ __forceinline__ int dws_xoff(int n, int q) {
-#if DWS_XSWZ
-    return 16 * n + 4 * (q ^ ((n >> 2) & 3));
-#else
-    return 16 * n + 4 * q;
-#endif
-}
+__device__ __forceinline__ int dws_xoff(int n, int q) { return 16 * n + 4 * (q ^ ((n >> 2) & 3)); }
 __device__ __forceinline__ dwm_bf16x8 dws_tr_fragment_x(const unsigned short* tile, int lane) {
-#if DWS_XSWZ
     typedef __attribute__((address_space(3))) dwm_s16x4 lds_s16x4;
     const int o = dws_xoff(lane >> 2, lane & 3);
     const dwm_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(tile + o));
     const dwm_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(tile + 256 + o));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-#else
-    return dwm_tr_fragment(tile, lane);
-#endif
 }
 
 template <int K, int NS>
@@ -109,23 +71,17 @@ struct DwStreamGeom {
 // with the folded BatchNorm-2 coefficients, no statistics -- ConvBNActivate's "dw" stage with frozen statistics (asr.py:27-37, 49)
 // F16 (EV only): the stored tensors hold IEEE fp16 (inference at precision "fp16"): the loaded words ARE the matrix operand -- no
 // conversion while staging --, the taps are split into fp16 digits, the output is rounded to fp16
-#ifndef DWS_FWD_MINW
-#define DWS_FWD_MINW 4        /* A/B: workgroups per CU the register allocation must allow (8: all 2048 channels of a wide layer resident at once) */
-#endif
-#ifndef DWS_FWD_PADLDS
-#define DWS_FWD_PADLDS 0      /* A/B: bytes of unused LDS per workgroup (caps the workgroups per CU: 26000 -> 4, 18000 -> 5) */
-#endif
 template <int K, int NT, int D, int CP = 0, int NS = 2, bool EV = false, bool F16 = false>
-__global__ __launch_bounds__(256, (NS == 2 && !EV) ? DWS_FWD_MINW : 4) void dwconv_fwd16_stream_kernel(DwParams p) {
+__global__ __launch_bounds__(256, 4) void dwconv_fwd16_stream_kernel(DwParams p) {
     static_assert(!F16 || EV, "fp16 storage: inference only");
     using S_ = DwStreamGeom<K, NS>;
     constexpr int STEPS = S_::STEPS, WPAD = S_::WPAD, WLEN = S_::WLEN, NL = S_::NL;
     constexpr int IMGP = S_::FWD_IMG > 512 * NL + 64 ? S_::FWD_IMG : 512 * NL + 64;   // + the staged runs of lanes past the row
-    __shared__ __attribute__((aligned(16))) unsigned short lds_img[4 * IMGP + ((NS == 2 && !EV) ? DWS_FWD_PADLDS / 2 : 0)];
+    __shared__ __attribute__((aligned(16))) unsigned short lds_img[4 * IMGP];
     __shared__ float lds_w[256];                             // WLEN used; every thread stores one slot (no lane-masked branch)
     __shared__ float lds_red[4][2];
 
-    const int c = dws_chan(blockIdx.x, p.C), g = blockIdx.y;
+    const int c = v100_chan_of_block<16>(blockIdx.x, p.C), g = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int n_ = lane & 15, q_ = lane >> 4;
@@ -348,29 +304,12 @@ __global__ __launch_bounds__(256, (NS == 2 && !EV) ? DWS_FWD_MINW : 4) void dwco
 // coefficients are known writes fmaf(dz1, p, fmaf(a1, q, r)) rounded to bf16: exactly the value (same operations, same order) the
 // consumers' on-load transform produced, so every downstream result is bit-identical.  The row loop is unrolled MAXR times (rows past
 // a wave's last one run as the branch-free kernel's dummy rows); B <= 4 MAXR.
-#ifndef DWS_BWD_MINW
-#define DWS_BWD_MINW 3        /* A/B: 2 = the plain fused backward at the kept-rows form's occupancy */
-#endif
-#ifndef DWS_BWD_PADLDS
-#define DWS_BWD_PADLDS 0
-#endif
-#ifndef DWS_DA1_K3
-#define DWS_DA1_K3 0          /* kept-rows form: kernel sizes up to this keep three workgroups per CU (168 registers) */
-#endif
-// DWS_DA1_KEEP 0 (A/B): the rows are NOT kept -- the plain form (rolled row loop, dz1 stored as produced, three workgroups per CU), then each
-// wave reads its own rows back (dz1 it wrote, a1 it read: L2 / Infinity Cache) and overwrites dz1 with the finished gradient.  Bit-identical
-// (the stored bf16 dz1 IS what the kept register held) but measured SLOWER in the step: this kernel 0.498 ms against 0.448 kept-rows and
-// 0.374 without DA1 (step 3.36 / 3.33 / 3.36 ms): the second pass costs more than the occupancy returns.
-#ifndef DWS_DA1_KEEP
-#define DWS_DA1_KEEP 1
-#endif
+// DA1 exists for rows of up to 512 outputs only (NS = 2).  Storing dz1 and reading the wave's rows back instead of keeping them, for
+// NS = 2 or for rows of 513 .. 768 outputs, was no net gain: DESIGN_rejected.md, "round 6 -- finished gradient da1 for time-stretched rows".
+// Workgroups per CU: 2 with the kept rows (they fill the register file), 3 without.
 template <int K, int NT, int D, int CP = 0, int NS = 2, bool DA1 = false, int MAXR = 8>
-__global__ __launch_bounds__(256, (DA1 && DWS_DA1_KEEP && NS == 2 && K > DWS_DA1_K3) ? 2 : DWS_BWD_MINW) void dwconv_bwd16_stream_kernel(DwParams p) {
-    // rows of up to 512 outputs: the wave KEEPS its rows in registers; rows of 513 .. 768 (NS = 3: 12 registers a row, the file is full)
-    // take the read-back form -- dz1 stored as produced, then each wave reads its own rows of dz1 and a1 back (L2 / Infinity Cache) and
-    // overwrites dz1 with the finished gradient.  Measured (round 6, stretch-110 step): this kernel 0.416 -> 0.610 ms, the two expand
-    // GEMMs -0.19 ms: no net gain -- off by default (V100_IR_DA1_TMAX, depthwise_bwd_fused16g.hip)
-    constexpr bool KEEP = DA1 && DWS_DA1_KEEP && NS == 2;
+__global__ __launch_bounds__(256, DA1 ? 2 : 3) void dwconv_bwd16_stream_kernel(DwParams p) {
+    static_assert(!DA1 || NS == 2, "the kept-rows form: rows of up to 512 outputs");
     using S_ = DwStreamGeom<K, NS>;
     constexpr int STEPS = S_::STEPS, WPAD = S_::WPAD, WLEN = S_::WLEN, IB = S_::IB, NL = S_::NL, XIMG = S_::XIMG;
     constexpr int IMG0 = S_::FWD_IMG > S_::BWD_IMG ? S_::FWD_IMG : S_::BWD_IMG;
@@ -378,12 +317,12 @@ __global__ __launch_bounds__(256, (DA1 && DWS_DA1_KEEP && NS == 2 && K > DWS_DA1
     constexpr int WAVE_U16 = IMGP + XIMG;
     constexpr int E_FLOATS = 16 * IB * DWM_EP;
     constexpr int LDS_BYTES = (4 * WAVE_U16 * 2 > 4 * E_FLOATS * 4) ? 4 * WAVE_U16 * 2 : 4 * E_FLOATS * 4;
-    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES + DWS_BWD_PADLDS];      // (DWS_BWD_PADLDS: A/B of the occupancy alone)
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
     __shared__ float lds_w[256];
     __shared__ float lds_red[4][2];
     __shared__ float lds_fin[4];
 
-    const int c = dws_chan(blockIdx.x, p.C), g = blockIdx.y;
+    const int c = v100_chan_of_block<16>(blockIdx.x, p.C), g = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int n_ = lane & 15, q_ = lane >> 4;
@@ -426,7 +365,7 @@ __global__ __launch_bounds__(256, (DA1 && DWS_DA1_KEEP && NS == 2 && K > DWS_DA1
     // taps, and parked in LDS: fetched by thread 0 at the end of the kernel they were three dependent misses between the channel's last
     // row and the stores of all its kept rows
     float fmu = 0.f, frs = 0.f, fga = 0.f;
-    if constexpr (DA1 && DWS_TAIL) { fmu = p.fin.a[c]; frs = p.fin.b[c]; fga = p.fin.gamma[c]; }
+    if constexpr (DA1) { fmu = p.fin.a[c]; frs = p.fin.b[c]; fga = p.fin.gamma[c]; }
     // BatchNorm-2 backward finalised HERE (DwPre, one group): its slab and parameter reads go out in front of the rows
     DwPreRegs prer;
     const bool pre_fast = p.pre.f.mode != 0 && p.pre.parts <= DW_PRE_MAXPARTS;
@@ -438,7 +377,7 @@ __global__ __launch_bounds__(256, (DA1 && DWS_DA1_KEEP && NS == 2 && K > DWS_DA1
     __builtin_amdgcn_sched_barrier(0);
 
     lds_w[threadIdx.x] = (tj >= 0 && tj < K) ? tapv : 0.f;
-    if constexpr (DA1 && DWS_TAIL) { lds_fin[0] = fmu; lds_fin[1] = frs; lds_fin[2] = fga; }      // (every thread, the same values: no branch)
+    if constexpr (DA1) { lds_fin[0] = fmu; lds_fin[1] = frs; lds_fin[2] = fga; }      // (every thread, the same values: no branch)
     const int off = (-p.pad) & 7;
     const int in0a = (-p.pad) & ~7;
     const int lpad = -in0a;
@@ -495,19 +434,19 @@ __global__ __launch_bounds__(256, (DA1 && DWS_DA1_KEEP && NS == 2 && K > DWS_DA1
     for (int ib = 0; ib < IB; ++ib) eacc[ib] = dwm_f32x4{0.f, 0.f, 0.f, 0.f};
     float s0 = 0.f, s1 = 0.f;
 
-    dwm_u32x2 keep_o[KEEP ? MAXR : 1][NS], keep_a[KEEP ? MAXR : 1][NS];
+    dwm_u32x2 keep_o[DA1 ? MAXR : 1][NS], keep_a[DA1 ? MAXR : 1][NS];
     auto row = [&](Row& rw, int r, auto rconst) {
         constexpr int RI = decltype(rconst)::value;  // DA1: the row's slot in the kept arrays (a compile-time index: registers)
         // (DA1: r is a constant in each of the eight unrolled copies, so `ok` and the five coefficient selects below would be hoisted
         //  out of all of them and live across the whole loop: 40 registers.  An opaque copy of nrows keeps them inside their row.)
         int nrows_l = nrows;
-        if constexpr (KEEP) asm volatile("" : "+s"(nrows_l));
+        if constexpr (DA1) asm volatile("" : "+s"(nrows_l));
         const bool ok = r < nrows_l;                 // rows past the end: zero coefficients -> g' = 0, xin = 0, mask 0, nothing stored
         const float ra = ok ? ca : 0.f, rb = ok ? cb : 0.f, rc = ok ? cc : 0.f, roa = ok ? oa : 0.f, rob = ok ? ob : 0.f;
         float auxv[NS][4];
 #pragma unroll
         for (int sub = 0; sub < NS; ++sub) {
-            if constexpr (KEEP) keep_a[RI][sub] = rw.a[sub];      // (before issue() below re-uses rw for the next row)
+            if constexpr (DA1) keep_a[RI][sub] = rw.a[sub];      // (before issue() below re-uses rw for the next row)
 #pragma unroll
             for (int e = 0; e < 4; ++e) auxv[sub][e] = dwm_elem(rw.a[sub], e);
         }
@@ -565,16 +504,16 @@ __global__ __launch_bounds__(256, (DA1 && DWS_DA1_KEEP && NS == 2 && K > DWS_DA1
                 outv[e] = yv;
             }
             const dwm_u32x2 o2 = {dwm_pack_rne(outv[0], outv[1]), dwm_pack_rne(outv[2], outv[3])};
-            if constexpr (KEEP) keep_o[RI][sub] = o2;
+            if constexpr (DA1) keep_o[RI][sub] = o2;
             else __builtin_amdgcn_raw_buffer_store_b64(o2, ry, (ok && in_row) ? 2 * t0 : 0x7ffffff0, (int)yb, CP);
         }
-        if constexpr (KEEP) (void)yb;
+        if constexpr (DA1) (void)yb;
         asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);          // rows are not interleaved: the sums of a row retire before the next row starts
     };
 
     using R0 = std::integral_constant<int, 0>;
-    if constexpr (KEEP) {
+    if constexpr (DA1) {
         static_assert(D >= 1 && D <= 4, "the kept-rows form keeps one to four rows of loads in flight");
 #define DWS_ROW(i_) if constexpr ((i_) < MAXR) row(raw[(i_) % D], (i_), std::integral_constant<int, ((i_) < MAXR ? (i_) : 0)>{});
         DWS_ROW(0) DWS_ROW(1) DWS_ROW(2) DWS_ROW(3) DWS_ROW(4) DWS_ROW(5) DWS_ROW(6) DWS_ROW(7)
@@ -609,9 +548,9 @@ __global__ __launch_bounds__(256, (DA1 && DWS_DA1_KEEP && NS == 2 && K > DWS_DA1
             p.wpartial[((size_t)g * p.C + c) * K + (K - 1 - jf)] = sum;
         }
     };
-    constexpr bool TAIL_FIRST = DA1 && DWS_TAIL;      // the kept rows leave first; the weight-gradient tiles follow under their stores
+    // DA1: the kept rows leave first; the weight-gradient tiles follow under their stores
     __syncthreads();
-    if constexpr (!TAIL_FIRST) {
+    if constexpr (!DA1) {
         e_exchange();
         __syncthreads();
     }
@@ -624,61 +563,26 @@ __global__ __launch_bounds__(256, (DA1 && DWS_DA1_KEEP && NS == 2 && K > DWS_DA1
         const float t1s = (lds_red[0][1] + lds_red[1][1]) + (lds_red[2][1] + lds_red[3][1]);
         p.stats[((size_t)g * p.C + c) * 2 + 0] = t0s;
         p.stats[((size_t)g * p.C + c) * 2 + 1] = t1s;
-        if constexpr (TAIL_FIRST) dw_finalize_bwd_pre(p.fin, c, (double)t0s, (double)t1s, lds_fin[0], lds_fin[1], lds_fin[2], lds_coef);
-        else if constexpr (DA1) dw_finalize_d(p.fin, c, (double)t0s, (double)t1s, lds_coef);      // (p, q, r) of BatchNorm 1's backward -> LDS too
+        if constexpr (DA1) dw_finalize_bwd_pre(p.fin, c, (double)t0s, (double)t1s, lds_fin[0], lds_fin[1], lds_fin[2], lds_coef);
         else if (p.fin.mode != 0) dw_finalize(p.fin, c, t0s, t1s);
     }
     if constexpr (DA1) {
         __syncthreads();
         const float pa = lds_coef[0], qb = lds_coef[1], rc = lds_coef[2];
-        if constexpr (KEEP) {
 #pragma unroll
-            for (int ri = 0; ri < MAXR; ++ri) {
-                const bool ok = ri < nrows;
-                const unsigned yb = row_bytes(ok ? ri : 0);
+        for (int ri = 0; ri < MAXR; ++ri) {
+            const bool ok = ri < nrows;
+            const unsigned yb = row_bytes(ok ? ri : 0);
 #pragma unroll
-                for (int sub = 0; sub < NS; ++sub) {
-                    const int t0 = 256 * sub + 16 * n_ + 4 * q_;
-                    float dv[4];
+            for (int sub = 0; sub < NS; ++sub) {
+                const int t0 = 256 * sub + 16 * n_ + 4 * q_;
+                float dv[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) dv[e] = fmaf(dwm_elem(keep_o[ri][sub], e), pa, fmaf(dwm_elem(keep_a[ri][sub], e), qb, rc));
-                    const dwm_u32x2 o2 = {dwm_pack_rne(dv[0], dv[1]), dwm_pack_rne(dv[2], dv[3])};
-                    __builtin_amdgcn_raw_buffer_store_b64(o2, ry, (ok && t0 < T) ? 2 * t0 : 0x7ffffff0, (int)yb, CP);
-                }
-            }
-        } else {
-            // the wave's own rows again, four at a time: 4 NS loads of dz1 (as stored above by this wave: the stores are older in its
-            // memory queue) and of a1 in flight, then the finished rows over the unfinished ones
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            for (int r0 = 0; r0 < nrows; r0 += 4) {
-                dwm_u32x2 go[4][NS], ga[4][NS];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const bool ok = r0 + i < nrows;
-                    const unsigned yb = row_bytes(ok ? r0 + i : 0);
-#pragma unroll
-                    for (int sub = 0; sub < NS; ++sub) {
-                        const int t0 = 256 * sub + 16 * n_ + 4 * q_;
-                        go[i][sub] = __builtin_amdgcn_raw_buffer_load_b64(ry, (ok && t0 < T) ? 2 * t0 : 0x7ffffff0, (int)yb, 0);
-                        ga[i][sub] = __builtin_amdgcn_raw_buffer_load_b64(raux, ok ? vo_aux[sub] : 0x7ffffff0, (int)yb, 0);
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const bool ok = r0 + i < nrows;
-                    const unsigned yb = row_bytes(ok ? r0 + i : 0);
-#pragma unroll
-                    for (int sub = 0; sub < NS; ++sub) {
-                        const int t0 = 256 * sub + 16 * n_ + 4 * q_;
-                        float dv[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) dv[e] = fmaf(dwm_elem(go[i][sub], e), pa, fmaf(dwm_elem(ga[i][sub], e), qb, rc));
-                        const dwm_u32x2 o2 = {dwm_pack_rne(dv[0], dv[1]), dwm_pack_rne(dv[2], dv[3])};
-                        __builtin_amdgcn_raw_buffer_store_b64(o2, ry, (ok && t0 < T) ? 2 * t0 : 0x7ffffff0, (int)yb, CP);
-                    }
-                }
+                for (int e = 0; e < 4; ++e) dv[e] = fmaf(dwm_elem(keep_o[ri][sub], e), pa, fmaf(dwm_elem(keep_a[ri][sub], e), qb, rc));
+                const dwm_u32x2 o2 = {dwm_pack_rne(dv[0], dv[1]), dwm_pack_rne(dv[2], dv[3])};
+                __builtin_amdgcn_raw_buffer_store_b64(o2, ry, (ok && t0 < T) ? 2 * t0 : 0x7ffffff0, (int)yb, CP);
             }
         }
+        e_exchange();                          // (every wave passed two barriers since its last image read: the images are dead)
     }
-    if constexpr (TAIL_FIRST) e_exchange();           // (every wave passed two barriers since its last image read: the images are dead)
 }

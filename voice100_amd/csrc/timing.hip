@@ -8,7 +8,6 @@
 #include <vector>
 #include <mutex>
 #include <atomic>
-#include <stdlib.h>
 
 namespace {
 struct Pair { hipEvent_t a, b; int tag; double bytes; };
@@ -113,7 +112,6 @@ extern "C" long long v100_launch_count(void) { return g_v100_launches.load(std::
 // Device-copy yardstick for the HBM-bound kernels (bench.py `copy_probe_gbs`): dst[i] = src[i] in 16-byte pieces, U independent
 // loads in flight per thread before the first store, workgroups of 256 threads walking the buffer grid-stride.
 // n16 = number of 16-byte pieces.  Same ABI conventions as every other entry point (device pointers, no sync).
-// V100_COPY_VARIANT (tuning only): digit 1 = unroll (1: 4, 2: 8, 3: 2), digit 2 = nontemporal (0 plain, 1 nt), digit 3 = workgroups per CU.
 template <int U, bool NT_>
 __global__ __launch_bounds__(256) void copy_probe_kernel(const f32x4* __restrict__ src, f32x4* __restrict__ dst, long long n16) {
     const long long stride = (long long)gridDim.x * 256;
@@ -133,19 +131,8 @@ __global__ __launch_bounds__(256) void copy_probe_kernel(const f32x4* __restrict
 extern "C" int v100_copy_probe(const void* src, void* dst, long long nbytes, void* stream) {
     if (!src || !dst) return V100_ERR_NULL;
     if (nbytes <= 0 || (nbytes & 15)) return V100_ERR_SHAPE;
-    // default 111 = one workgroup per CU, nontemporal, 4 pieces in flight per lane: the fastest of profiles/r03_copy_probe_variants.txt
-    static const int variant = [] { const char* e = getenv("V100_COPY_VARIANT"); return e ? atoi(e) : 111; }();
-    const int un = variant % 10, nt = (variant / 10) % 10, wpc = variant / 100 > 0 ? variant / 100 : 8;
-    const dim3 grid(256 * wpc), block(256);
-    const f32x4* s = (const f32x4*)src;
-    f32x4* d = (f32x4*)dst;
-    const long long n16 = nbytes / 16;
-    hipStream_t st = (hipStream_t)stream;
-#define CP(U_, N_) V100_GGL((copy_probe_kernel<U_, N_>), grid, block, 0, st, s, d, n16)
-    if (un == 2) { if (nt) CP(8, true); else CP(8, false); }
-    else if (un == 3) { if (nt) CP(2, true); else CP(2, false); }
-    else { if (nt) CP(4, true); else CP(4, false); }
-#undef CP
+    // one workgroup per CU, nontemporal, 4 pieces in flight per lane: the fastest of profiles/r03_copy_probe_variants.txt
+    V100_GGL((copy_probe_kernel<4, true>), dim3(256), dim3(256), 0, (hipStream_t)stream, (const f32x4*)src, (f32x4*)dst, nbytes / 16);
     return v100_launch_status();
 }
 

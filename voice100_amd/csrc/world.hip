@@ -26,7 +26,6 @@
 #include "common.h"
 #include "../../include/voice100_hip.h"
 #include "world_f64.h"
-#include <stdlib.h>
 
 namespace {
 constexpr int NF = 512, NH = 256, NB = 257;          // fft size, half, bins of the fp32 wave-per-pulse kernel (16 kHz)
@@ -260,9 +259,6 @@ __global__ __launch_bounds__(256) void world_timebase_kernel(WorldParams p) {
 constexpr int TBC_CH = 8192, TBC_NFR = 128, TBC_NT = 1024;          // samples per chunk of the chained time base; contour frames staged per chunk
 struct TbChain { int* ticket; int* cflag; double* cval; int* nflag; int* nval; int nchunks; };
 
-#ifdef TBC_DEBUG
-__device__ long long g_tbc_dbg[8 * 64];
-#endif
 __global__ __launch_bounds__(TBC_NT) void world_timebase_chain_kernel(WorldParams p, TbChain ch) {
     constexpr int CH = TBC_CH, NFR = TBC_NFR, NTH = TBC_NT, PER = CH / NTH, NW = NTH / 64, PL = NTH / 64;     // PL: per-thread sums a lane of the scanning wave takes
     // s_tot[TI(j)]: one pad slot per PER entries, so that the scans' per-thread runs of PER consecutive samples (thread stride PER + 1 doubles)
@@ -280,12 +276,6 @@ __global__ __launch_bounds__(TBC_NT) void world_timebase_chain_kernel(WorldParam
     if (tid == 0) s_chunk = atomicAdd(ch.ticket + b, 1);
     __syncthreads();
     const int c = s_chunk, c0 = c * CH;
-#ifdef TBC_DEBUG          /* -DTBC_DEBUG: wall-clock stamps of utterance 0's chunks (tools/tbc_timeline.py): how the 64-way bank conflict of the first version was found */
-#define TBC_STAMP(slot) if (tid == 0 && b == 0) g_tbc_dbg[c * 8 + (slot)] = wall_clock64()
-#else
-#define TBC_STAMP(slot)
-#endif
-    TBC_STAMP(0);
     if (T < 2 || ylen < 2) {
         if (c == 0 && tid == 0) p.n_pulses[b] = 0;
         return;
@@ -340,7 +330,6 @@ __global__ __launch_bounds__(TBC_NT) void world_timebase_chain_kernel(WorldParam
         vuv[i] = voiced ? 1 : 0;
         s_tot[TI(1 + j)] = 2.0 * kPi * fi / fs;
     }
-    TBC_STAMP(1);
     // ---- the running phase at this chunk's first sample: from the predecessor's mailbox ----
     if (tid == 0) {
         double a0 = 0.0;
@@ -357,7 +346,6 @@ __global__ __launch_bounds__(TBC_NT) void world_timebase_chain_kernel(WorldParam
         s_first = n;                                      // first sample at which the sum has left the binade (n: none)
     }
     __syncthreads();
-    TBC_STAMP(2);
     const double A0 = s_carry;
     bool serial = !(A0 > 0.0) && c > 0;                  // (a non-positive running phase: degenerate input)
     double u = 0.0, lim = 0.0;
@@ -497,7 +485,6 @@ __global__ __launch_bounds__(TBC_NT) void world_timebase_chain_kernel(WorldParam
         }
         __syncthreads();
     }
-    TBC_STAMP(3);
     // ---- hand the running phase on, then the work that nobody waits for ----
     if (tid == 0 && !last) {
         __hip_atomic_store(cval + c, s_tot[TI(n)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -505,7 +492,6 @@ __global__ __launch_bounds__(TBC_NT) void world_timebase_chain_kernel(WorldParam
     }
     for (int j = tid; j <= n; j += NTH) s_tot[TI(j)] = fmod(s_tot[TI(j)], 2.0 * kPi);      // in place: nobody needs the unwrapped phase any more
     __syncthreads();
-    TBC_STAMP(4);
     // crossings between samples i and i + 1, i = c0 - 1 + j (i >= 0): thread t owns the PER consecutive j of its run, so the pulse order
     // is thread order: count, one workgroup scan, place behind the predecessors' pulses
     unsigned hits = 0;
@@ -558,7 +544,6 @@ __global__ __launch_bounds__(TBC_NT) void world_timebase_chain_kernel(WorldParam
             ++slot;
         }
     }
-    TBC_STAMP(5);
 }
 #undef TI
 
@@ -1134,9 +1119,6 @@ extern "C" int v100_world_decode_aperiodicity(const float* coded, float* ap, lon
 static int world_ymax(int T, int fs, double frame_period_ms) { return (int)((double)T * frame_period_ms * (double)fs / 1000.0); }
 
 // bytes of the `workspace` argument of v100_world_synthesize
-#ifdef TBC_DEBUG
-extern "C" int v100_tbc_debug_read(long long* host) { return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_tbc_dbg), sizeof(long long) * 8 * 64) == hipSuccess ? 0 : 2; }
-#endif
 extern "C" long long v100_world_synth_workspace_bytes(int B, int T, int fs, double frame_period_ms, int fft_size, int max_pulses) {
     if (B <= 0 || T <= 0 || fs <= 0 || fft_size < 64 || fft_size > 2048 || (fft_size & (fft_size - 1)) || max_pulses <= 0 || frame_period_ms <= 0) return -1;
     const long long Y = (world_ymax(T, fs, frame_period_ms) + 63) & ~63LL;
@@ -1187,9 +1169,7 @@ extern "C" int v100_world_synthesize(const float* f0, const float* sp, const flo
     hipStream_t st = (hipStream_t)stream;
     WorldParams pt = p;
     pt.Ymax = (int)Y;                   // workspace rows are Y long; y rows are Ymax long (kernels 1 and 2 only touch the workspace)
-    static const bool tb_serial_env = []() { const char* e = getenv("V100_WORLD_TB_SERIAL"); return e && e[0] == '1'; }();     // A/B: one workgroup per utterance
-    const bool tb_serial = (tb_serial_env && serial_fits) || !chain_fits;
-    if (tb_serial) V100_GGL(world_timebase_kernel, dim3((unsigned)B), dim3(256), 0, st, pt);
+    if (!chain_fits) V100_GGL(world_timebase_kernel, dim3((unsigned)B), dim3(256), 0, st, pt);
     else {
         if (hipMemsetAsync(chain0, 0, chain_bytes, st) != hipSuccess) return V100_ERR_LAUNCH;
         V100_GGL(world_timebase_chain_kernel, dim3((unsigned)((Ymax + TBC_CH - 1) / TBC_CH), (unsigned)B), dim3(TBC_NT), 0, st, pt, ch);
