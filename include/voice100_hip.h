@@ -333,6 +333,25 @@ int v100_dwconv_bwd_da1_io(const void* g, const void* g2, const float* w, const 
                            const void* xpre, const float* xa, const float* xb, void* da1_out, float* stats, float* dw,
                            const float* bn1_gamma, const float* bn1_mean, const float* bn1_rstd, float* pqr, float* dgamma,
                            float* dbeta, int B, int C, int T, int K, void* stream);
+/* The eval-mode depthwise stage on 16-bit hidden tensors (inference at precision "bf16" / "fp16"), as the block executor issues it --
+ * exposed for the kernel tests (tests/test_gpu_eval_dw_oracle.py):
+ *   h2[b][c][t] = round16(relu6(fmaf(sum_j h1[b][c][t - (K-1)/2 + j] * q(w[c][j]), out_a[c], out_b[c]))),  t < T, zeros outside [0, T)
+ * with fp32 accumulation; q = ONE rounding of the fp32 tap to the storage format (bf16; all 24 bits with V100_DW_DIGITS=3, which
+ * the fp16 form does not read).  flags: 1 = channel-major, 2 = fp16 (else bf16).
+ * Operands: h1 and h2 are [B][C][P], or [C][B][P] when channel-major, P = v100_row_pitch16(T, B); w [C][K] and out_a / out_b [C] fp32
+ * (the folded BatchNorm 2).  The pitch padding [T, P) of a row:
+ *   h1: the 8-sample run that straddles T is LOADED whole (elements [T, (T + 7) & ~7) are read), and every element at or past T is
+ *       replaced by zero before it is used: the result does not depend on the padding's bits (NaN included).  The producing GEMM
+ *       makes no promise about them either: batch-major (epilogue 2, 16-bit Y) it stores whole 4-sample groups, so
+ *       [T, (T + 3) & ~3) of a row holds relu6(fmaf(acc, ea, eb)) of columns that are not part of the tensor and the rest of the
+ *       padding is never written; channel-major the whole [C][B P] matrix is ONE GEMM and the padding columns are ordinary
+ *       output columns (relu6 of whatever their X columns held).
+ *   h2: stored in whole 4-sample groups: [T, (T + 3) & ~3) is overwritten with values that are NOT part of the result (the window
+ *       at those positions still reaches real samples) -- finite for finite operands --; [(T + 3) & ~3, P) is not written.
+ * K: odd and one of the specialised sizes (v100_dw_mfma_supported).  T <= 768: the streaming kernel, both layouts and formats;
+ * longer rows: the general kernel, bf16 and [B][C][P] only.  Anything else returns 1, NULL operands 3 (no fallback). */
+int v100_dwconv_fwd_eval_io(const void* h1, const float* w, const float* out_a, const float* out_b, void* h2, int B, int C, int T,
+                            int K, int flags, void* stream);
 /* the two block-boundary passes with a bf16-stored operand: io16 of v100_chan_reduce2_io: 2 = v is bf16 (sums of dy, dy*a3);
  * of v100_chan_affine2_io: 1 = u is bf16 (y = s3*a3 + t3 (+ x)), 6 = v and out are bf16 (da3 = p*dy + q*a3 + r) */
 int v100_chan_reduce2_io(const void* u, const void* v, float* partial, int G, int B, int C, int T, int io16, void* stream);

@@ -61,7 +61,7 @@ def test_block_channel_major_equals_batch_major(cuda, k):
 @pytest.mark.parametrize("precision,tol", [("bf16", 3e-2), ("fp16", 4e-3)])
 def test_block_channel_major_vs_fp32(cuda, precision, tol):
     """Against the exact-fp32 eval path (the parity path, held to the oracle at 1e-4): bf16 at the bf16 bar; fp16 -- fp16 operands,
-    fp16-stored hidden tensors, two fp16 digits per depthwise tap -- at 4e-3."""
+    fp16-stored hidden tensors, depthwise taps rounded to fp16 (one digit: tests/test_gpu_eval_dw_oracle.py) -- at 4e-3."""
     for (cin, cout, k, res, B, T) in ((256, 256, 35, True, 9, 51), (256, 512, 51, False, 4, 128), (512, 512, 83, True, 16, 51), (512, 512, 59, True, 3, 400)):
         blk = _block(cuda, cin, cout, k, res, k + B)
         x = torch.randn(B, cin, T, generator=torch.Generator().manual_seed(T)).to(cuda)

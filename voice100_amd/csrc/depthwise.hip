@@ -468,6 +468,13 @@ int dw_fwd_eval_io(const void* h1, const float* w, const float* out_a, const flo
     return v100_launch_status();
 }
 
+// The same call as a C-ABI entry point, for the kernel tests (tests/test_gpu_eval_dw_oracle.py: float64, element by element); the block
+// executor keeps calling the function above.  flags: 1 = channel-major tensors [C][B][P], 2 = the tensors hold fp16.
+extern "C" int v100_dwconv_fwd_eval_io(const void* h1, const float* w, const float* out_a, const float* out_b, void* h2, int B, int C, int T,
+                                       int K, int flags, void* stream) {
+    return dw_fwd_eval_io(h1, w, out_a, out_b, h2, B, C, T, K, stream, flags & 1, (flags >> 1) & 1);
+}
+
 extern "C" int v100_dwconv_bwd_io(const void* g, const void* g2, const float* w, const float* ga, const float* gb, const float* gc,
                                   const void* xpre, const float* xa, const float* xb, void* dxin, float* stats, float* wpartial,
                                   float* dw, int G, int B, int C, int T, int K, int io16, void* stream) {

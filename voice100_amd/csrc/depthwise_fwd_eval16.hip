@@ -9,7 +9,8 @@ bool dw_launch_fwd_eval16(const DwParams& p, hipStream_t st, const V100TimedLaun
     if (f16) {
         if (!(p.stride == 1 && p.upsample == 1 && !p.flip && p.Tin == p.Tout && p.Tin <= 768 && p.pad == (p.K - 1) / 2)) return false;
         dim3 grid(p.C, p.G);
-        // two fp16 digits per tap: 22 mantissa bits, far below the fp16 rounding of the stored activations
+        // ONE fp16 digit per tap (DW_DIGITS16: the first digit of dwm_split_f16, the tap rounded to fp16 like the stored activations;
+        // two digits up to round 5).  V100_DW_DIGITS is not read here.
 #define X(KK)                                                                                                                           \
     if (p.K == KK) {                                                                                                                    \
         if (p.Tin <= 512) V100_LAUNCH(tl, (dwconv_fwd16_stream_kernel<KK, DW_DIGITS16, DWS_DEPTH, DWS_CP, 2, true, true>), grid, dim3(256), 0, st, p);  \
