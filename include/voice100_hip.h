@@ -580,6 +580,24 @@ int v100_world_unnormalize_v2(const float* x, float* f0, float* logspc, float* c
                               const float* ls_mean, const float* ls_std, const float* ca_mean, const float* ca_std,
                               int B, int T, int S, int Cap, void* stream);
 
+/* ---- sample-rate conversion (csrc/resample.hip): torchaudio.functional.resample's default method ("sinc_interpolation", Hann
+ * window) for a rate pair reduced to o / n (orig / gcd, new / gcd).  An utterance of len samples gives
+ * v100_resample_out_len(len, o, n) = ceil(n len / o) outputs (a HOST helper, 64-bit: 2^31 - 1 samples at 16 -> 22.05 kHz pass
+ * 2^31 outputs; -1 on len < 0, o < 1 or n < 1), and
+ *   y[q n + p] = sum_j K[p][j] x[q o + j - width],  x zero outside [0, len),
+ * K the [n][2 width + o] polyphase bank.  A phase's taps are non-zero on at most 2 width + 1 consecutive positions, so the kernel
+ * takes the bank in COMPACT form: starts [n] int (first tap kept of each phase, floor(p o / n) as voice100_amd.audio_io builds
+ * it) and taps [n][L] fp32 (row p = K[p][starts[p] .. starts[p] + L), zero where that runs past the dense row), both on the device.
+ * x [B][Nmax], y [B][Mmax] fp32; lens [B] int32 on the device, NULL = every row has Nmax samples (entries are clamped to
+ * [0, Nmax]).  The kernel writes row b's min(out_len, Mmax) outputs, zeros from there to Mmax, and that count to out_lens[b]
+ * (NULL = not wanted).  fp32 fused multiply-adds in tap order, so a row's values do not depend on what else is in the batch.
+ * One workgroup serves v100_resample_tile() consecutive outputs of one utterance.  1 on B, Nmax, Mmax, o, n, width or L < 1 and
+ * on B > 65535; 3 on a NULL x, taps, starts or y. */
+long long v100_resample_out_len(long long len, int o, int n);
+int v100_resample_tile(void);
+int v100_resample_sinc(const float* x, const int* lens, const float* taps, const int* starts, float* y, int* out_lens, int B,
+                       int Nmax, int Mmax, int o, int n, int width, int L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,9 +5,9 @@ n_fft, power 2, HTK mel scale, no norm) followed by log(mel.T + 1e-6).
 
 The framed real DFT is a dense [2*257 x 400] x [400 x T] product (window folded into the basis) and the
 filterbank a [64 x 257] x [257 x T] one; both run on the exact-fp32 MFMA GEMM kernel, with three small
-HBM-bound kernels around them (framing, power, log+transpose).  File decoding / resampling stay on the
-host (torchaudio), as in the reference.  PARITY UNPINNED against torchaudio itself (absent here): checked
-against oracle/mel.py and torch.stft.
+HBM-bound kernels around them (framing, power, log+transpose).  A file path is decoded on the host by
+audio_io.load_wav (WAV only) and brought to the module's rate on the GPU by audio_io.resample: no torchaudio.
+PARITY UNPINNED against torchaudio itself (absent here): checked against oracle/mel.py and torch.stft.
 """
 import math
 
@@ -116,14 +116,10 @@ class MelSpectrogramAudioTransform(nn.Module):
         return out[0] if squeeze else out
 
     def forward(self, audio) -> torch.Tensor:
-        """A path (as in the reference: decode + resample on the host with torchaudio, then the GPU transform)
-        or an already-loaded waveform tensor."""
+        """A path to a WAV file (as in the reference: load, first channel, resample to the module's rate, transform) or an
+        already-loaded waveform tensor.  The module must be on the GPU: the resampling runs there too."""
         if isinstance(audio, torch.Tensor):
             return self.transform(audio)
-        try:
-            import torchaudio
-        except ImportError as e:
-            raise RuntimeError("loading audio files needs torchaudio (not installed); pass a waveform tensor") from e
-        waveform, sr = torchaudio.load(audio)
-        waveform = torchaudio.functional.resample(waveform[0], sr, self.sample_rate)
-        return self.transform(waveform.to(self.dft_basis.device))
+        from .audio_io import load_wav, resample
+        waveform, sr = load_wav(audio)
+        return self.transform(resample(waveform[0].to(self.dft_basis.device), sr, self.sample_rate))
