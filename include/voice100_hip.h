@@ -598,6 +598,30 @@ int v100_resample_tile(void);
 int v100_resample_sinc(const float* x, const int* lens, const float* taps, const int* starts, float* y, int* out_lens, int B,
                        int Nmax, int Mmax, int o, int n, int width, int L, void* stream);
 
+/* ---- K19 WORLD feature statistics (csrc/world_stat.hip): one accumulation step of voice100/calc_stat.py:40-56 over a padded batch.
+ * f0 [B][T], logspc [B][T][S], codeap [B][T][A] fp32, f0_len [B] int32, all on the device and contiguous (4-byte alignment is
+ * enough).  Frame (b, t) is valid iff t < min(max(f0_len[b], 0), T).  The call ADDS to moments, float64 [4 + 2S + 2A]:
+ *   [0]               sum of f0 over valid frames with f0 > 30.0f
+ *   [1]               sum of f0^2 over the same frames
+ *   [2]               the number of those frames
+ *   [3]               the number of valid frames
+ *   [4 .. 4+S)        sum of logspc per column over valid frames
+ *   [4+S .. 4+2S)     sum of logspc^2 per column over valid frames
+ *   [4+2S .. 4+2S+A)  sum of codeap per band over valid frames with codeap < -0.2f (tested per element)
+ *   [4+2S+A .. end)   sum of codeap^2 per band over the same elements
+ * Every product and sum is float64 (the products are exact); the two thresholds are compared in fp32, as torch compares an fp32
+ * tensor with a Python scalar (f0 == 30.0f and codeap == (float)-0.2 are excluded).  An invalid frame is never loaded, so the
+ * padding may hold NaN or Inf; a NaN in a valid frame propagates for logspc and fails both tests for f0 and codeap.  Sums of
+ * shards add: moments of two calls, processes or ranks may be added element by element.
+ * Two launches, no floating-point atomics, bit-identical from run to run: workgroups write partial rows of 4 + 2S + 2A doubles
+ * (partial: v100_world_stat_parts(B, T, S) rows, a function of the three only; need not be zeroed), a second launch adds the rows
+ * -- 64 runs of consecutive rows, each in index order, the 64 sums then pairwise in a fixed order -- and then adds the total to moments.
+ * 1 <= S <= 1024, 1 <= A <= 8, B >= 1, T >= 1; anything else returns 1 (v100_world_stat_parts: -1), a NULL pointer 3, both before
+ * anything touches a device. */
+int v100_world_stat_parts(int B, int T, int S);
+int v100_world_stat_accum(const float* f0, const int* f0_len, const float* logspc, const float* codeap, double* partial,
+                          double* moments, int B, int T, int S, int A, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
