@@ -466,6 +466,17 @@ int v100_ctc_greedy_decode(const float* logits, const int* lens, long long* out,
  * back_ws: B*T*(2*Lmax+1) int16; path [B][T] int32 = index into the blank-expanded labels; score [B]. */
 int v100_ctc_best_path(const float* logp, const long long* labels, const int* in_len, const int* lab_len, void* back_ws, int* path,
                        float* score, int B, int T, int V, int Lmax, int max_move, void* stream);
+/* K20, forced alignment in one launch (csrc/align.hip): the Viterbi of v100_ctc_best_path with everything voice100/align_text.py:39-56
+ * writes per utterance.  path [B][T] int32 and score [B] are bit-identical to v100_ctc_best_path; best_labels [B][T] int64 is the
+ * blank-extended label at each path position; align [B][2*Lmax+1] int32 is the number of frames the path spends at each extended
+ * position (0 beyond 2*lab_len+1); path and best_labels are 0 beyond in_len.  in_len / lab_len may be NULL (T / Lmax everywhere).
+ * moves_ws: v100_ctc_align_workspace_bytes(B, T, Lmax) bytes (one byte per frame and state; 0 = unsupported shape).
+ * T <= 12000, 2*Lmax+1 <= 4096, 1 <= max_move <= 8, else 1; a NULL pointer 3; both before anything touches a device.
+ * v100_ctc_align_block(): frames per staged block of emissions (lengths around it and its multiples are the kernel's seams). */
+long long v100_ctc_align_workspace_bytes(int B, int T, int Lmax);
+int v100_ctc_align_block(void);
+int v100_ctc_align(const float* logp, const long long* labels, const int* in_len, const int* lab_len, void* moves_ws, int* path,
+                   long long* best_labels, int* align, float* score, int B, int T, int V, int Lmax, int max_move, void* stream);
 /* TextToAlignTextModel.align (voice100/models/tts.py:89-110) batched: text [B][Lmax] int64, align [B][Lmax][2] float64
  * (gap, length), out [B][Tmax] int64 (zero padded; rows longer than Tmax are cut), out_len [B].  out == NULL: only out_len is
  * written (head + int(sum(align)) + tail per utterance), so the caller can size `out` with one read-back. */

@@ -1,6 +1,7 @@
 """Integer decode / alignment steps on the GPU, bit-exact with the reference:
 greedy CTC decoding (argmax + merge_repeated, voice100/text.py:99-104), ctc_best_path forced alignment
-(voice100/models/align.py:18-66), TextToAlignTextModel.align (voice100/models/tts.py:89-110) and the v2
+(voice100/models/align.py:18-66) and the one-launch forced alignment built on it (ctc_align: path, labels, durations and
+score, voice100/align_text.py:39-56), TextToAlignTextModel.align (voice100/models/tts.py:89-110) and the v2
 TextToAlignText.align (voice100/models/_align_v2.py:48-73)."""
 import torch
 
@@ -37,6 +38,33 @@ def ctc_best_path(log_probs: torch.Tensor, labels: torch.Tensor, input_lengths=N
     ext = torch.zeros((B, 2 * L + 1), dtype=torch.int64, device=lp.device)
     ext[:, 1::2] = labels
     return score, path, torch.gather(ext, 1, path.long())
+
+
+def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, input_lengths=None, label_lengths=None, max_move: int = 3):
+    """Forced alignment in one launch (K20, csrc/align.hip): log_probs [B, T, V] fp32, labels [B, L] int64 ->
+    (score [B], path [B, T] int32, best_labels [B, T] int64, align [B, 2L+1] int32).
+
+    score and path are bit-identical to ctc_best_path; best_labels are the blank-extended labels on the path; align[b, s] is the
+    number of frames utterance b spends at extended position s -- the row voice100/align_text.py:49-51 writes.  path and
+    best_labels are 0 beyond each input length, align beyond 2 * label_length + 1."""
+    if not log_probs.is_cuda:
+        raise RuntimeError("ctc_align: GPU tensors only")
+    lp = log_probs.contiguous().float()
+    B, T, V = lp.shape
+    labels = labels.to(device=lp.device, dtype=torch.int64).contiguous()
+    L = labels.shape[1]
+    il = input_lengths.to(device=lp.device, dtype=torch.int32).contiguous() if input_lengths is not None else None
+    ll = label_lengths.to(device=lp.device, dtype=torch.int32).contiguous() if label_lengths is not None else None
+    nbytes = N.helper("v100_ctc_align_workspace_bytes", B, T, L)
+    if nbytes <= 0:
+        raise RuntimeError(f"ctc_align: unsupported shape (T = {T} <= 12000 and 2 L + 1 = {2 * L + 1} <= 4096 are the limits)")
+    moves = torch.empty((nbytes,), dtype=torch.uint8, device=lp.device)
+    path = torch.empty((B, T), dtype=torch.int32, device=lp.device)
+    best = torch.empty((B, T), dtype=torch.int64, device=lp.device)
+    align = torch.empty((B, 2 * L + 1), dtype=torch.int32, device=lp.device)
+    score = torch.empty((B,), dtype=torch.float32, device=lp.device)
+    N.call("v100_ctc_align", lp, labels, il, ll, moves, path, best, align, score, B, T, V, L, int(max_move))
+    return score, path, best, align
 
 
 def align_expand(text: torch.Tensor, align: torch.Tensor, text_len=None, head: int = 5, tail: int = 5):

@@ -18,7 +18,8 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
-__all__ = ["shard_indices", "scatter_run", "TTSPipeline", "TTSPipelineV2", "ASRPipeline", "GraphedForward"]
+__all__ = ["shard_indices", "scatter_run", "TTSPipeline", "TTSPipelineV2", "ASRPipeline", "AlignPipeline", "align_records",
+           "GraphedForward"]
 
 
 def shard_indices(n_items: int, rank: int, world: int, mode: str = "contiguous") -> torch.Tensor:
@@ -210,6 +211,52 @@ class ASRPipeline:
         feats = self.mel(wav_or_mel) if self.mel is not None else wav_or_mel
         ids, n = ctc_greedy_decode(self.model(feats))
         return ids, n
+
+
+class AlignPipeline:
+    """The loop body of voice100/align_text.py:39-56 for one batch, on the device:
+
+        audio [B, T, audio_size], audio_len [B], text [B, Lmax] int64, text_len [B]
+          -> model._forward_btv                            logits [B, T_out, V], logits_len      (AudioAlignCTC or AudioToAlignText)
+          -> torch.log_softmax                             a stock op: the kernel's additions stay those of the reference
+          -> decode.ctc_align, one launch                  Viterbi over min(logits_len, text_len) labels (align.py:147), path,
+                                                           labels on the path, durations, scores    (K20, csrc/align.hip)
+
+    Returns {"score" [B] fp32: the per-utterance best-path scores (the reference's ctc_best_path drops them, align.py:161),
+    "hist" [B, T_out] int32: positions in the blank-extended text, "path" [B, T_out] int64: the labels there, "path_len" [B],
+    "align" [B, 2 Lmax + 1] int32: frames per extended position, laid out for the ORIGINAL text_len and 0 beyond}.
+    The module must be in eval mode: dropout would randomise the alignments."""
+
+    def __init__(self, model, max_move: int = 3):
+        self.model, self.max_move = model, int(max_move)
+
+    @torch.no_grad()
+    def __call__(self, audio: torch.Tensor, audio_len: torch.Tensor, text: torch.Tensor, text_len: torch.Tensor):
+        from .decode import ctc_align
+        if self.model.training:
+            raise RuntimeError("AlignPipeline: the model is in training mode (call model.eval(): dropout would randomise the alignment)")
+        if not audio.is_cuda:
+            raise RuntimeError("AlignPipeline: GPU tensors only")
+        logits, logits_len = self.model._forward_btv(audio, audio_len)
+        lp = torch.log_softmax(logits, dim=-1)
+        dev = lp.device
+        logits_len = logits_len.to(dev)
+        lab_len = torch.minimum(logits_len, text_len.to(dev))            # for very short audio (align.py:147)
+        score, hist, path, align = ctc_align(lp, text.to(dev), logits_len, lab_len, self.max_move)
+        return {"score": score, "hist": hist, "path": path, "path_len": logits_len, "align": align}
+
+
+def align_records(out, text: torch.Tensor, text_len: torch.Tensor, decode: Callable[[torch.Tensor], str]) -> List[str]:
+    """The lines `raw_text|raw_align_text|align` of voice100/align_text.py:48-56 for one AlignPipeline result (no newline).
+    `decode` is the caller's tokenizer.decode (ids tensor -> str); one device-to-host copy per tensor, then CPU string work."""
+    path, path_len, align = out["path"].cpu(), out["path_len"].cpu(), out["align"].cpu()
+    text, text_len = text.cpu(), text_len.cpu()
+    lines = []
+    for i in range(path.shape[0]):
+        n = int(text_len[i])
+        durations = " ".join(str(int(x)) for x in align[i, :2 * n + 1])
+        lines.append(decode(text[i, :n]) + "|" + decode(path[i, :int(path_len[i])]) + "|" + durations)
+    return lines
 
 
 class GraphedForward:
