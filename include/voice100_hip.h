@@ -189,6 +189,17 @@ int v100_log_transpose(const float* in, float* out, int B, int C, int T, float o
 int v100_log_mel_fused(const float* x, float* out, const float* window, const float* tw256, const float* tw512, const int* mel_start,
                        const int* mel_count, const float* mel_w, int B, int N, int T, int hop, int n_fft, int n_mels, float log_offset,
                        void* stream);
+/* K21: the same kernel body over a batch of utterances of different lengths, padded as the reference's collate pads
+ * (generate_audio_text_batch, data_modules.py:446-455: each utterance transformed alone, then pad_sequence with log(1e-6)).
+ * x [B][N] fp32, lengths [B] int32 on the device (entries are clamped to [0, N]); with n = lengths[b] and
+ * T_b = n > n_fft / 2 ? 1 + n / hop : 0, frames t < T_b of out [B][T][n_mels] are those of v100_log_mel_fused on x[b][0 .. n) alone,
+ * bit for bit (the reflection is taken at n), frames t >= T_b hold `fill` (the caller passes (float)log(log_offset), what
+ * pad_sequence writes; no device logf), and out_len[b] = T_b (int32, device).  x[b][i] is never read for i >= n.  T may be
+ * smaller than 1 + N / hop (the caller knows the longest utterance: T = 1 + max(lengths) / hop); frames t >= T are not written,
+ * out_len[b] is T_b all the same.  Status as v100_log_mel_fused, plus 3 on a NULL lengths or out_len. */
+int v100_log_mel_fused_len(const float* x, const int* lengths, float* out, int* out_len, const float* window, const float* tw256,
+                           const float* tw512, const int* mel_start, const int* mel_count, const float* mel_w, int B, int N, int T,
+                           int hop, int n_fft, int n_mels, float log_offset, float fill, void* stream);
 /* AlignTextToAudioModel.predict epilogue (tts.py:197-200, _layers_v1.py:132-138): x [B][T][2+S+Cap] ->
  * f0 = gate(x0 < 0 ? 0 : x1*std+mean), logspc, codeap un-normalised */
 int v100_world_unnormalize(const float* x, float* f0, float* logspc, float* codeap, const float* f0_mean, const float* f0_std,

@@ -204,6 +204,46 @@ def resample(waveform: torch.Tensor, orig_freq, new_freq, lengths=None, lowpass_
     return y[0] if waveform.dim() == 1 else y
 
 
+def load_batch(paths, sample_rate, device=None):
+    """A list of WAV files -> (wave [B, Mmax] float32, zero beyond each utterance, wave_len [B] int32), both on the device, in
+    the order of `paths`: per file what the reference's transforms do (load, first channel, resample to `sample_rate`:
+    data_modules.py:287-292), row b equal to resample(load_wav(paths[b])[0][0], its rate, sample_rate).  The files are grouped by
+    their own rate; a group is one padded block, one host-to-device copy and one resample(..., lengths=) launch, and its rows
+    are scattered to their places by one indexed copy.  Files already at `sample_rate` are copied through."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("load_batch: voice100_amd runs on the GPU only (no CPU fallback): the resampling runs on the device")
+    paths = list(paths)
+    if not paths:
+        raise ValueError("load_batch: no paths")
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"load_batch: voice100_amd runs on the GPU only (got device {device})")
+    _rates(sample_rate, sample_rate)                                  # a positive integer, or ValueError
+    target = int(sample_rate)
+    groups = {}                                                       # source rate -> [(row, first channel)]
+    for row, path in enumerate(paths):
+        waveform, sr = load_wav(path)
+        if waveform.shape[1] < 1:
+            raise ValueError(f"{path}: no samples")
+        groups.setdefault(sr, []).append((row, waveform[0]))
+    done = []                                                         # (rows, y [G, M], y_len [G])
+    for sr, items in groups.items():
+        rows = torch.tensor([r for r, _ in items], dtype=torch.int64)
+        lens = torch.tensor([w.shape[0] for _, w in items], dtype=torch.int32)
+        block = torch.zeros((len(items), int(lens.max())), dtype=torch.float32)
+        for g, (_, w) in enumerate(items):
+            block[g, :w.shape[0]] = w
+        y, y_len = resample(block.to(device), sr, target, lengths=lens)
+        done.append((rows.to(device), y, y_len))
+    B, width = len(paths), max(y.shape[1] for _, y, _ in done)
+    wave = torch.zeros((B, width), dtype=torch.float32, device=device)
+    wave_len = torch.empty((B,), dtype=torch.int32, device=device)
+    for rows, y, y_len in done:
+        wave[:, :y.shape[1]].index_copy_(0, rows, y)
+        wave_len.index_copy_(0, rows, y_len)
+    return wave, wave_len
+
+
 class WORLDAudioProcessor(nn.Module):
     """voice100's WORLDAudioProcessor (data_modules.py:295-316): a file path -> (f0, logspc or mcep, codeap), float32 CPU tensors
     as `WORLDVocoder.encode` returns them.  The reference reads the file through sox (`remix 1`: the first channel; `rate`: to

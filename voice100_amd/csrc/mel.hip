@@ -13,6 +13,11 @@
 //   out[b][t][:].
 // The waveform is read once from HBM, the output written once; no frames / spec / power tensors.  fp32 throughout, twiddles and
 // window from tables computed in double by the caller; error against a float64 FFT ~1e-6 of the frame's largest bin.
+//
+// K21, the same body for a batch of utterances of different lengths (v100_log_mel_fused_len): row b holds lengths[b] samples, its
+// frames are those the reference computes for the utterance alone (reflection at the utterance's own end) and the rest of the
+// row is the collate's padding value, so one launch gives what generate_audio_text_batch builds (data_modules.py:446-455).
+#include <type_traits>
 #include "common.h"
 #include "../../include/voice100_hip.h"
 
@@ -29,6 +34,11 @@ struct MelParams {
     float log_offset;
     long frames;
 };
+struct MelParamsLen : MelParams {      // the ragged entry's own arguments (kept out of MelParams: the dense kernel's code stays as it was)
+    const int* lengths;        // [B] samples of each utterance
+    int* out_len;              // [B] frames of each utterance
+    float fill;                // what the frames beyond an utterance's last hold
+};
 struct cplx { float re, im; };
 __device__ __forceinline__ cplx cmul(cplx a, cplx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
 __device__ __forceinline__ cplx cadd(cplx a, cplx b) { return {a.re + b.re, a.im + b.im}; }
@@ -43,10 +53,16 @@ __device__ __forceinline__ int rev4x4(int k) {          // reverse the four base
     return ((k & 3) << 6) | (((k >> 2) & 3) << 4) | (((k >> 4) & 3) << 2) | ((k >> 6) & 3);
 }
 
-__global__ __launch_bounds__(256) void log_mel_fused_kernel(MelParams p) {
+// The whole kernel.  RAGGED: row b is an utterance of lengths[b] samples -- the reflection is taken at ITS end, its frames beyond
+// 1 + lengths[b] / hop are `fill`, and no sample beyond lengths[b] is read; the frame arithmetic is the same instruction sequence.
+template <class Params>
+__global__ __launch_bounds__(256) void log_mel_fused_kernel(Params p) {
+    constexpr bool RAGGED = std::is_same<Params, MelParamsLen>::value;
     __shared__ float2 zbuf[4][256];
     __shared__ float pbuf[4][260];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // (the ragged kernel keeps its wave number, and with it the frame's (b, t), in scalar registers: its length load has one
+    // address for the wave and its branch and row addresses are scalar work; the dense kernel's code is left as it was)
+    const int lane = threadIdx.x & 63, wave = RAGGED ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     float2* z = zbuf[wave];
     float* pw = pbuf[wave];
     // frame-invariant per-lane constants: window at this lane's 8 samples, twiddles of its butterflies
@@ -77,6 +93,17 @@ __global__ __launch_bounds__(256) void log_mel_fused_kernel(MelParams p) {
     for (long f = (long)blockIdx.x * 4 + wave; f < p.frames; f += stride) {
         const int b = (int)(f / p.T), t = (int)(f - (long)b * p.T);
         const float* xb = p.x + (size_t)b * p.N;
+        int n = p.N;                                       // samples of this row: where the reflection is taken
+        if constexpr (RAGGED) {
+            n = min(max(p.lengths[b], 0), p.N);                // one wave-uniform load; entries are clamped to [0, N]
+            // the utterance has T_b = n > n_fft / 2 ? 1 + n / hop : 0 frames (torch's reflect pad needs more than n_fft / 2 samples)
+            if (t == 0 && lane == 0) p.out_len[b] = n > 256 ? 1 + n / p.hop : 0;
+            if (n <= 256 || t * p.hop > n) {                   // t >= T_b, wave-uniform: the collate's padding value, nothing loaded
+                if (lane < p.n_mels) p.out[((size_t)b * p.T + t) * p.n_mels + lane] = p.fill;
+                continue;
+            }
+            // t < T_b: the largest index is (n / hop) hop + 255 <= n + 255, so one reflection lands in [n - 257, n)
+        }
         const int base = t * p.hop - 256;                  // waveform index of frame sample 0 (center = True: n_fft / 2 of padding)
         cplx a[4];
 #pragma unroll
@@ -86,7 +113,7 @@ __global__ __launch_bounds__(256) void log_mel_fused_kernel(MelParams p) {
             for (int e = 0; e < 2; ++e) {
                 int i = base + 2 * (lane + 64 * q) + e;
                 i = i < 0 ? -i : i;                            // reflect (no edge repeat), torch.stft pad_mode="reflect"
-                i = i >= p.N ? 2 * (p.N - 1) - i : i;
+                i = i >= n ? 2 * (n - 1) - i : i;
                 const float w = wn[q][e];
                 v[e] = w != 0.f ? xb[i] * w : 0.f;             // the window is zero outside its 400 samples: those are not loaded
             }
@@ -140,17 +167,33 @@ __global__ __launch_bounds__(256) void log_mel_fused_kernel(MelParams p) {
         asm volatile("" ::: "memory");                        // the next frame's stage-0 stores stay behind these reads
     }
 }
+
+int check_mel_shape(int B, int N, int T, int hop, int n_fft, int n_mels) {
+    if (B <= 0 || T <= 0 || hop <= 0 || n_fft != 512 || n_mels <= 0 || n_mels > 64 || N <= n_fft / 2) return V100_ERR_SHAPE;
+    if ((long)(T - 1) * hop > N) return V100_ERR_SHAPE;
+    return V100_OK;
+}
+long mel_blocks(long frames) { return min((frames + 3) / 4, 4096L); }      // one wave per frame, grid-stride beyond 4 x 4096
 }   // namespace
 
 extern "C" int v100_log_mel_fused(const float* x, float* out, const float* window, const float* tw256, const float* tw512,
                                   const int* mel_start, const int* mel_count, const float* mel_w, int B, int N, int T, int hop,
                                   int n_fft, int n_mels, float log_offset, void* stream) {
     if (!x || !out || !window || !tw256 || !tw512 || !mel_start || !mel_count || !mel_w) return V100_ERR_NULL;
-    if (B <= 0 || T <= 0 || hop <= 0 || n_fft != 512 || n_mels <= 0 || n_mels > 64 || N <= n_fft / 2) return V100_ERR_SHAPE;
-    if ((long)(T - 1) * hop > N) return V100_ERR_SHAPE;
+    if (int rc = check_mel_shape(B, N, T, hop, n_fft, n_mels)) return rc;
     MelParams p{x, out, window, tw256, tw512, mel_start, mel_count, mel_w, B, N, T, hop, n_mels, log_offset, (long)B * T};
-    long blocks = (p.frames + 3) / 4;
-    if (blocks > 4096) blocks = 4096;
-    V100_GGL(log_mel_fused_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+    V100_GGL(log_mel_fused_kernel<MelParams>, dim3((unsigned)mel_blocks(p.frames)), dim3(256), 0, (hipStream_t)stream, p);
+    return v100_launch_status();
+}
+
+extern "C" int v100_log_mel_fused_len(const float* x, const int* lengths, float* out, int* out_len, const float* window,
+                                      const float* tw256, const float* tw512, const int* mel_start, const int* mel_count,
+                                      const float* mel_w, int B, int N, int T, int hop, int n_fft, int n_mels, float log_offset,
+                                      float fill, void* stream) {
+    if (!x || !lengths || !out || !out_len || !window || !tw256 || !tw512 || !mel_start || !mel_count || !mel_w) return V100_ERR_NULL;
+    if (int rc = check_mel_shape(B, N, T, hop, n_fft, n_mels)) return rc;
+    MelParamsLen p{{x, out, window, tw256, tw512, mel_start, mel_count, mel_w, B, N, T, hop, n_mels, log_offset, (long)B * T},
+                   lengths, out_len, fill};
+    V100_GGL(log_mel_fused_kernel<MelParamsLen>, dim3((unsigned)mel_blocks(p.frames)), dim3(256), 0, (hipStream_t)stream, p);
     return v100_launch_status();
 }

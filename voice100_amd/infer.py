@@ -200,17 +200,37 @@ class TTSPipelineV2:
 
 class ASRPipeline:
     """BASELINE configs[4] per replica: waveform chunks [B, N] fp32 (16 kHz) -> log-mel [B, T, 64] -> AudioToTextCTC logits
-    -> greedy CTC ids [B, T'] int64 (zero padded) + lengths (data_modules.py:276-291, asr.py:110-116, text.py:99-104)."""
+    -> greedy CTC ids [B, T'] int64 (zero padded) + lengths (data_modules.py:276-291, asr.py:110-116, text.py:99-104).
+
+    With `lengths` the rows are utterances of their own lengths: samples per row when the pipeline has a `mel` (the features
+    and their frame counts then come from one ragged launch, mel.transform(wav, lengths)), frames per row when it has none
+    (wav_or_mel is the padded feature batch); the decode stops at model.output_length(frames) of each row."""
 
     def __init__(self, model, mel=None):
         self.model, self.mel = model, mel
 
     @torch.no_grad()
-    def __call__(self, wav_or_mel: torch.Tensor):
+    def __call__(self, wav_or_mel: torch.Tensor, lengths=None):
         from .decode import ctc_greedy_decode
-        feats = self.mel(wav_or_mel) if self.mel is not None else wav_or_mel
-        ids, n = ctc_greedy_decode(self.model(feats))
-        return ids, n
+        if lengths is None:
+            feats = self.mel(wav_or_mel) if self.mel is not None else wav_or_mel
+            return ctc_greedy_decode(self.model(feats))
+        if self.mel is not None:
+            feats, audio_len = self.mel.transform(wav_or_mel, lengths)
+        else:
+            feats, audio_len = wav_or_mel, torch.as_tensor(lengths).to(wav_or_mel.device)
+        return ctc_greedy_decode(self.model(feats), self.model.output_length(audio_len))
+
+    def transcribe(self, paths, decode: Callable[[torch.Tensor], str]) -> List[str]:
+        """WAV files -> their transcripts: audio_io.load_batch, the ragged pipeline, then `decode` (the caller's tokenizer.decode,
+        ids tensor -> str, as in align_records) on each row's ids; one device-to-host copy per tensor.  Needs a `mel`."""
+        from .audio_io import load_batch
+        if self.mel is None:
+            raise RuntimeError("ASRPipeline.transcribe: the pipeline has no mel transform to turn waveforms into features")
+        wave, wave_len = load_batch(paths, self.mel.sample_rate, self.mel.dft_basis.device)
+        ids, n = self(wave, wave_len)
+        ids, n = ids.cpu(), n.cpu()
+        return [decode(ids[i, :int(n[i])]) for i in range(ids.shape[0])]
 
 
 class AlignPipeline:

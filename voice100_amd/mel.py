@@ -83,14 +83,48 @@ class MelSpectrogramAudioTransform(nn.Module):
     def audio_size(self) -> int:
         return self.n_mels
 
-    def num_frames(self, n_samples: int) -> int:
+    def num_frames(self, n_samples):
+        """Frames of an utterance of n_samples samples (an int, or a tensor of them: the result has its dtype and device)."""
+        if isinstance(n_samples, torch.Tensor):
+            return 1 + torch.div(n_samples, self.hop_length, rounding_mode="floor")
         return 1 + n_samples // self.hop_length
 
+    def _host_lengths(self, lengths, B: int, n: int):
+        """`lengths` as a tensor, its shape checked against the batch and, when it lives on the host, every entry against
+        [n_fft / 2 + 1, n] (device lengths are not read back).  Returns (tensor, the longest entry or None)."""
+        lens = torch.as_tensor(lengths)
+        if lens.shape != (B,):
+            raise ValueError(f"MelSpectrogramAudioTransform: lengths must be [{B}], got {tuple(lens.shape)}")
+        if lens.dtype.is_floating_point or lens.dtype == torch.bool:
+            raise ValueError(f"MelSpectrogramAudioTransform: lengths must be integers, got {lens.dtype}")
+        if lens.is_cuda:
+            return lens, None
+        lo = self.n_fft // 2 + 1
+        host = lens.tolist()
+        for b, v in enumerate(host):
+            if not lo <= v <= n:
+                raise ValueError(f"MelSpectrogramAudioTransform: lengths[{b}] = {v} is outside [{lo}, {n}] (the reflect padding "
+                                 f"needs more than n_fft / 2 = {self.n_fft // 2} samples, and the row holds {n})")
+        return lens, max(host)
+
     @torch.no_grad()
-    def transform(self, waveform: torch.Tensor, fused: bool = None) -> torch.Tensor:
+    def transform(self, waveform: torch.Tensor, lengths=None, fused: bool = None):
         """waveform [N] or [B, N] fp32 on the GPU -> log-mel [T, n_mels] or [B, T, n_mels].  One launch (csrc/mel.hip: FFT per wave)
         for the reference's configuration; `fused=False` (or any other n_fft / filter count) takes the framing + DFT-GEMM +
-        filterbank-GEMM kernels."""
+        filterbank-GEMM kernels.
+
+        With `lengths` ([B] integers, CPU or device) every row of waveform [B, N] is an utterance of its own length and the result is
+        (audio [B, T, n_mels] fp32, audio_len [B] int32 on the device), the batch the reference's collate builds
+        (generate_audio_text_batch, data_modules.py:446-455): row b's first audio_len[b] = 1 + lengths[b] // hop frames are those of
+        transform(waveform[b, :lengths[b]]), bit for bit (the reflection is taken at the utterance's own end), the rest is
+        log(log_offset), and what the waveform holds beyond lengths[b] is never read.  One launch; fused kernel only
+        (NotImplementedError with fused=False or a configuration without it).
+          * CPU lengths are checked (each in [n_fft / 2 + 1, N], ValueError naming the row otherwise -- torch's reflect pad raises
+            there too) and the batch is as wide as its longest utterance, T = 1 + max(lengths) // hop (pad_sequence's width).
+          * Device lengths are not read back: T = 1 + N // hop, entries are clamped to [0, N], and a row with
+            lengths[b] <= n_fft / 2 comes back all log(log_offset) with audio_len[b] = 0."""
+        if lengths is not None:
+            return self._transform_ragged(waveform, lengths, fused)
         squeeze = waveform.dim() == 1
         x = waveform[None] if squeeze else waveform
         F_._check(x, "MelSpectrogramAudioTransform")
@@ -115,11 +149,34 @@ class MelSpectrogramAudioTransform(nn.Module):
         N.call("v100_log_transpose", mel, out, B, self.n_mels, T, float(self.log_offset))
         return out[0] if squeeze else out
 
-    def forward(self, audio) -> torch.Tensor:
+    def _transform_ragged(self, waveform, lengths, fused):
+        if waveform.dim() != 2 or waveform.shape[0] < 1:
+            raise ValueError(f"MelSpectrogramAudioTransform: lengths need a [B, N] waveform, B >= 1, got {tuple(waveform.shape)}")
+        B, n = waveform.shape
+        lens, longest = self._host_lengths(lengths, B, n)               # before any device work
+        if fused is False or not self.fused:
+            raise NotImplementedError("MelSpectrogramAudioTransform: lengths are served by the one-launch kernel only "
+                                      "(n_fft = 512, <= 64 filters of <= 32 bins; not with fused=False)")
+        F_._check(waveform, "MelSpectrogramAudioTransform")
+        x = waveform.contiguous()
+        T = self.num_frames(n if longest is None else longest)
+        lens = lens.to(x.device, torch.int32).contiguous()
+        out = torch.empty((B, T, self.n_mels), dtype=torch.float32, device=x.device)
+        out_len = torch.empty((B,), dtype=torch.int32, device=x.device)
+        with torch.cuda.device(x.device):
+            N.call("v100_log_mel_fused_len", x, lens, out, out_len, self._win512, self._tw256, self._tw512, self._mel_start,
+                   self._mel_count, self._mel_w, B, n, T, self.hop_length, self.n_fft, self.n_mels, float(self.log_offset),
+                   float(math.log(self.log_offset)))
+        return out, out_len
+
+    def forward(self, audio):
         """A path to a WAV file (as in the reference: load, first channel, resample to the module's rate, transform) or an
-        already-loaded waveform tensor.  The module must be on the GPU: the resampling runs there too."""
+        already-loaded waveform tensor.  A list or tuple of paths gives the padded batch and its lengths,
+        transform(*audio_io.load_batch(paths, sample_rate)).  The module must be on the GPU: the resampling runs there too."""
         if isinstance(audio, torch.Tensor):
             return self.transform(audio)
-        from .audio_io import load_wav, resample
+        from .audio_io import load_batch, load_wav, resample
+        if isinstance(audio, (list, tuple)):
+            return self.transform(*load_batch(audio, self.sample_rate, self.dft_basis.device))
         waveform, sr = load_wav(audio)
         return self.transform(resample(waveform[0].to(self.dft_basis.device), sr, self.sample_rate))
