@@ -325,6 +325,16 @@ int v100_pw_gemm_io(const void* A_bf16, const void* X, const void* X2, const flo
 int v100_pw_wgrad_io(const void* G, const void* G2, const float* ga, const float* gb, const float* gc, int g_mode,
                      const void* X, const float* xa, const float* xb, int x_mode, float* partial, float* dW, int S, int B,
                      int M, int K, int T, int io16, void* stream);
+/* Several such weight gradients in ONE launch (csrc/pointwise_bf16_wgrad_group.h), each workgroup carrying one tile through the
+ * whole contraction: no split-K slabs, no reduce launch.  The workgroup walks the contraction in the order of the S splits of
+ * v100_pw_wgrad_io and sums their partial tiles in slab order, so every dW equals v100_pw_wgrad_io(..., S, ...) bit for bit.
+ * Only the two finished-gradient forms of the InvertedResidual backward (asr.py:45-59; csrc/block.hip v100_ir_stack_bwd): g_mode 0,
+ * io16 = 1 | 4, x_mode 1 (project: M % 256 == 0, K % 128 == 0) or 0 (expand on da1: M % 128 == 0, K % 256 == 0), any S that takes.
+ * n <= 16 problems; ptrs (HOST, 5 per problem): G X xa xb dW; dims (HOST, 8 per problem): B M K T S g_mode x_mode io16.
+ * _supported: 1 when a problem qualifies (anything else makes v100_pw_wgrad_group return 1); _tiles: its workgroups. */
+int v100_pw_wgrad_group_supported(int B, int M, int K, int T, int S, int g_mode, int x_mode, int io16);
+int v100_pw_wgrad_group_tiles(int M, int K, int x_mode);
+int v100_pw_wgrad_group(int n, const void* const* ptrs, const int* dims, void* stream);
 int v100_dw_mfma_supported(int K, int stride);
 /* Row pitch, in elements, of every 16-bit-stored activation tensor [B][C][P] the _io entry points address: a multiple of 8 (16-byte
  * rows); for B > 1 and T >= 256 a multiple of 64 (rows start on 128-byte lines: a time-stretched 1136-byte row otherwise shares its
@@ -468,6 +478,17 @@ long long v100_ir_stack_plan(const int* desc, long long* plan);
 int v100_ir_stack_fwd_train(const int* desc, const void* const* params, const void* x, const void* x16, void* blob, void* stream);
 int v100_ir_stack_bwd(const int* desc, const void* const* params, const void* x, const void* x16, const void* blob, const void* dy,
                       void* dx, void* grads, void* ws, void* stream);
+/* v100_ir_stack_bwd defers the two 1x1 weight gradients (asr.py:47,51: the pw / pw-linear convs) of blocks on the finished-gradient
+ * path whose gradients both qualify for v100_pw_wgrad_group with >= min_problem_tiles tiles (32), keeps their operands da3 / da1
+ * in per-block regions of the backward workspace and flushes them in one grouped launch once >= min_flush_tiles (192) wait and the
+ * next block would not fit the same launch, or in the ordinary per-problem launches when the walk ends with fewer.  Same results.
+ * v100_ir_stack_wgrad_plan (HOST only, no GPU call) tells what happens for a descriptor: out = 3 per block {defers, byte offset of
+ * the block's region in ws or -1, flush right after this block's backward: tiles (> 0 grouped, < 0 per problem, 0 none)}, then
+ * {bwd_ws_bytes, bytes of the shared part in front of the regions}.  have_x16: the caller passes x16 (block 0 defers only then).
+ * v100_ir_stack_wgrad_group_thresholds replaces the two defaults process-wide (tests: the grouped path at small shapes); it
+ * changes bwd_ws_bytes of v100_ir_stack_plan, so set it before planning. */
+int v100_ir_stack_wgrad_plan(const int* desc, int have_x16, int min_problem_tiles, int min_flush_tiles, long long* out);
+int v100_ir_stack_wgrad_group_thresholds(int min_problem_tiles, int min_flush_tiles);
 
 /* ---- SURVEY 8(f) "next" rows: integer decode / alignment steps on the device (csrc/decode.hip), bit-exact ----
  * greedy CTC decode: argmax per frame (first maximum), collapse repeats, drop blanks (voice100/text.py:99-104);

@@ -55,6 +55,7 @@ def step_rows(B=32, T=1024):
     add("optim", "weight preparation: fp32 weights -> bf16 + transposed bf16 copies (1x1 weights only)", 0)      # filled below
     t = T
     w_pw = 0
+    n_grouped = 0
     for i, (cin, cout, k, s, res) in enumerate(SPEC):
         hid = 4 * cin
         tout = (t - 1) // s + 1
@@ -85,21 +86,33 @@ def step_rows(B=32, T=1024):
         dy = B * cout * (pitch16(tout) * 2 if dy16 else tout * 4)
         add("bn_pass", f"{L} BatchNorm-3 backward: dy, a3 -> da3 (sums + affine in one launch)", dy + 2 * B * cout * Po * e)
         S3, S1 = wgrad_splits(B, cout, hid), wgrad_splits(B, hid, cin)
-        add("pw_wgrad", f"{L} project weight gradient: da3, a2 -> dW3 (through {S3} partial slabs)", B * cout * Po * e + B * hid * Po * e + cout * hid * 4, fl3)
-        add("slab", f"{L} dW3 slab reduction ({S3} slabs written + read: {(2 * S3) * cout * hid * 4 / 1e6:.0f} MB, not algorithmic)", 0)
+        # the wide blocks (both gradients >= 32 tiles of the wave-specialised kernel, finished-gradient path: rows of <= 512 outputs,
+        # B <= 32) leave their two weight gradients to ONE grouped launch of the stack executor, a tile per workgroup through the whole
+        # contraction (block.hip, v100_ir_stack_bwd; pointwise_bf16_wgrad_group.h): same operand bytes, no partial slabs, no reduction
+        grouped = a16 and i > 0 and tout <= 512 and B <= 32 and (cout // 256) * (hid // 128) >= 32 and (hid // 128) * (cin // 256) >= 32
+        n_grouped += 2 * grouped
+        how3 = "in the grouped launch" if grouped else f"through {S3} partial slabs"
+        add("pw_wgrad", f"{L} project weight gradient: da3, a2 -> dW3 ({how3})", B * cout * Po * e + B * hid * Po * e + cout * hid * 4, fl3,
+            launches=0 if grouped else 1)
+        if not grouped:
+            add("slab", f"{L} dW3 slab reduction ({S3} slabs written + read: {(2 * S3) * cout * hid * 4 / 1e6:.0f} MB, not algorithmic)", 0)
         add("pw_gemm", f"{L} project backward-data: da3, W3^T, a2 (mask) -> dz2 + BN2-backward sums",
             B * cout * Po * e + cout * hid * 2 + 2 * B * hid * Po * e + parts_o * hid * 8, fl3)
         add("dw_bwd", f"{L} depthwise backward (data + weight fused): dz2, a2, a1 -> dz1, dWd",
             e * B * hid * (2 * Po + 2 * Pi) + 8 * hid * k + 8 * hid)
-        add("pw_wgrad", f"{L} expand weight gradient: dz1, a1 (BN1-backward affine), x -> dW1 partial slabs",
-            2 * B * hid * Pi * e + xin + hid * cin * 4, fl1)
-        add("slab", f"{L} dW1 slab reduction ({S1} slabs written + read: {(2 * S1) * hid * cin * 4 / 1e6:.0f} MB, not algorithmic)", 0)
+        how1 = "dW1 in the grouped launch" if grouped else "dW1 partial slabs"
+        add("pw_wgrad", f"{L} expand weight gradient: dz1, a1 (BN1-backward affine), x -> {how1}",
+            2 * B * hid * Pi * e + xin + hid * cin * 4, fl1, launches=0 if grouped else 1)
+        if not grouped:
+            add("slab", f"{L} dW1 slab reduction ({S1} slabs written + read: {(2 * S1) * hid * cin * 4 / 1e6:.0f} MB, not algorithmic)", 0)
         if i > 0:                                      # the first block's input gradient is not needed (the audio is a leaf without grad)
             add("pw_gemm", f"{L} expand backward-data: dz1, a1 (affine), W1^T (, dy) -> dx",
                 2 * B * hid * Pi * e + hid * cin * 2 + B * cin * (pitch16(t) * 2 if dx16 else t * 4) + (dy if res else 0), fl1)
         add("bn_fin", f"{L} BatchNorm finalisers backward (BN2 from the GEMM slab; BN1 inside the depthwise kernel)",
             parts_o * hid * 8 + 24 * hid, launches=1)
         t = tout
+    if n_grouped:
+        add("pw_wgrad", f"the grouped launch of the {n_grouped} weight gradients above (their bytes and flops are in their rows)", 0)
     # ---- head, loss
     Th = t
     # round 6: dropout's backward rides in the head's backward-data GEMM (one byte of mask per element there), the CTC gradient is

@@ -216,6 +216,31 @@ static size_t ir_bwd_carve(const int* sh, void* base, IrBwdWs& w) {
     return c.used + 256;
 }
 
+// ---- deferred weight gradients (stack executor).  A block on the finished-gradient path whose two 1x1 weight gradients are both
+// grouped-launch problems of at least min_tiles tiles can leave them to a later grouped launch: their operands are then da3 and
+// da1 (kept in a per-block region of the backward workspace), a2 and the block input's shadow (activation blob) and s2 / t2 (the
+// block's coefficient blob) -- nothing the rest of the backward walk overwrites.
+static size_t ir_defer_da3_bytes(const int* sh) {
+    const size_t n = (size_t)sh[IR_B] * sh[IR_COUT] * pitch16(conv_out(sh[IR_T], sh[IR_K], sh[IR_STRIDE]), sh[IR_B]) * 2;
+    return (n + 255) & ~size_t(255);
+}
+static size_t ir_defer_bytes(const int* sh) {
+    const size_t n = (size_t)sh[IR_B] * sh[IR_HID] * pitch16(sh[IR_T], sh[IR_B]) * 2;
+    return ir_defer_da3_bytes(sh) + ((n + 255) & ~size_t(255));
+}
+static int ir_wgrad_defer_tiles(const int* sh) {      // of both gradients
+    return v100_pw_wgrad_group_tiles(sh[IR_COUT], sh[IR_HID], 1) + v100_pw_wgrad_group_tiles(sh[IR_HID], sh[IR_CIN], 0);
+}
+static bool ir_wgrad_defer_ok(const int* sh, bool have_x16, int min_tiles) {
+    const int B = sh[IR_B], cin = sh[IR_CIN], hid = sh[IR_HID], cout = sh[IR_COUT], T = sh[IR_T], K = sh[IR_K];
+    if (sh[IR_ACT16] < 4 || !(sh[IR_PREPPED] & 2) || (sh[IR_PREPPED] & 8) || !have_x16 || sh[IR_STRIDE] != 1) return false;
+    if (!v100_ir_act16_supported(sh) || v100_dw_num_groups(B, hid) != 1 || !dw_bwd_da1_supported(B, hid, T, K, 1)) return false;
+    const int io = WG_IO_G | WG_IO_X;
+    return v100_pw_wgrad_group_supported(B, cout, hid, T, v100_pw_wgrad_splits(B, cout, hid), 0, 1, io) &&
+           v100_pw_wgrad_group_supported(B, hid, cin, T, v100_pw_wgrad_splits(B, hid, cin), 0, 0, io) &&
+           v100_pw_wgrad_group_tiles(cout, hid, 1) >= min_tiles && v100_pw_wgrad_group_tiles(hid, cin, 0) >= min_tiles;
+}
+
 extern "C" long long v100_ir_bwd_workspace_bytes(const int* shape) {
     IrBwdWs w;
     return (long long)ir_bwd_carve(shape, nullptr, w);
@@ -224,6 +249,7 @@ extern "C" long long v100_ir_bwd_workspace_bytes(const int* shape) {
 // ptrs: 0 x 1 a1 2 a2 3 a3 | 4 w1 5 wd 6 w3 | 7 g1 8 g2 9 g3 | 10 coef | 11 dy | 12 dx (may be NULL) |
 //       13 dW1 14 dg1 15 db1 16 dWd 17 dg2 18 db2 19 dW3 20 dg3 21 db3 | 22 workspace | 23 prepared weights (from forward)
 //       24 x16 (act16 >= 4 only, may be NULL): the bf16 shadow of x the forward read
+//       25 (read only with PREPPED bit 6, the stack executor's deferred weight gradients): the block's own da3 / da1 region
 extern "C" int v100_ir_bwd(const int* sh, const void* const* P, void* stream) {
     if (!sh || !P) return V100_ERR_NULL;
     const int B = sh[IR_B], cin = sh[IR_CIN], hid = sh[IR_HID], cout = sh[IR_COUT], T = sh[IR_T], K = sh[IR_K], S = sh[IR_STRIDE];
@@ -243,6 +269,16 @@ extern "C" int v100_ir_bwd(const int* sh, const void* const* P, void* stream) {
     const int dy16 = (sh[IR_PREPPED] & 16) ? 1 : 0, dx16 = (sh[IR_PREPPED] & 32) ? 1 : 0;
     IrBwdWs w;
     ir_bwd_carve(sh, const_cast<void*>(P[22]), w);
+    // PREPPED bit 6 (set by the stack executor only, ir_wgrad_defer_ok): the two 1x1 weight gradients are NOT launched here -- the
+    // executor runs them later, grouped with other blocks' (v100_pw_wgrad_group) -- so their G operands da3 and da1 go to the
+    // block's own region P[25] (da3, then da1 at ir_defer_da3_bytes), which outlives this call
+    const bool defer = (sh[IR_PREPPED] & 64) != 0;
+    if (defer) {
+        if (!P[25]) return V100_ERR_NULL;
+        if (sh[IR_ACT16] < 4) return V100_ERR_SHAPE;
+        w.da3 = (float*)P[25];
+        w.dz1 = (float*)((char*)const_cast<void*>(P[25]) + ir_defer_da3_bytes(sh));
+    }
     float *pp = w.pqr, *qq = w.pqr + mc, *rr = w.pqr + 2 * mc;
     int rc;
     IrPrep pw;
@@ -274,8 +310,9 @@ extern "C" int v100_ir_bwd(const int* sh, const void* const* P, void* stream) {
     if (sh[IR_ACT16]) {
         if (!v100_ir_act16_supported(sh)) return V100_ERR_SHAPE;
         const bool g16 = sh[IR_ACT16] >= 2;
-        CK(v100_pw_wgrad_io(w.da3, nullptr, nullptr, nullptr, nullptr, 0, a2, s2, t2, 1, w.slab, (float*)P[19], v100_pw_wgrad_splits(B, cout, hid),
-                            B, cout, hid, T2, WG_IO_X | (a316 ? WG_IO_G : 0), stream));
+        if (!defer)
+            CK(v100_pw_wgrad_io(w.da3, nullptr, nullptr, nullptr, nullptr, 0, a2, s2, t2, 1, w.slab, (float*)P[19], v100_pw_wgrad_splits(B, cout, hid),
+                                B, cout, hid, T2, WG_IO_X | (a316 ? WG_IO_G : 0), stream));
         const int parts16 = v100_pw_num_parts(B, T2);
         CK(v100_pw_gemm_io(pw.w3tbf, w.da3, nullptr, nullptr, nullptr, nullptr, 0, w.dz2, s2, t2, a2, 4, w.part, B, hid, cout, T2,
                            PW_IO_R | (g16 ? PW_IO_Y : 0) | (a316 ? PW_IO_X : 0), stream));
@@ -303,9 +340,11 @@ extern "C" int v100_ir_bwd(const int* sh, const void* const* P, void* stream) {
             CK(v100_bn_bwd_finalize(w.part, G16, (long long)B * T, g1, m1, r1, pp, qq, rr, (float*)P[14], (float*)P[15], hid, stream));
         }
         const void* x16 = (sh[IR_ACT16] >= 4 && (sh[IR_PREPPED] & 2)) ? P[24] : nullptr;
+        if (defer && !(da1 && x16)) return V100_ERR_SHAPE;   // (cannot happen: ir_wgrad_defer_ok tests what decides this path)
         if (da1) {
-            CK(v100_pw_wgrad_io(w.dz1, nullptr, nullptr, nullptr, nullptr, 0, x16 ? x16 : (const void*)x, nullptr, nullptr, 0, w.slab, (float*)P[13],
-                                v100_pw_wgrad_splits(B, hid, cin), B, hid, cin, T, WG_IO_G | (x16 ? WG_IO_X : 0), stream));
+            if (!defer)
+                CK(v100_pw_wgrad_io(w.dz1, nullptr, nullptr, nullptr, nullptr, 0, x16 ? x16 : (const void*)x, nullptr, nullptr, 0, w.slab, (float*)P[13],
+                                    v100_pw_wgrad_splits(B, hid, cin), B, hid, cin, T, WG_IO_G | (x16 ? WG_IO_X : 0), stream));
             if (dx)
                 CK(v100_pw_gemm_io(pw.w1tbf, w.dz1, nullptr, nullptr, nullptr, nullptr, 0, dx, nullptr, nullptr, res ? dy : nullptr, res ? 5 : 0, nullptr,
                                    B, cin, hid, T, PW_IO_X | ((dy16 && res) ? PW_IO_R : 0) | (dx16 ? PW_IO_Y : 0), stream));
@@ -529,7 +568,8 @@ extern "C" int v100_ir_prep_batched(const int* shapes, const void* const* w1s, c
 // segment's three or four): the per-block Python -> autograd -> ctypes crossings were 2/3 of the 3 ms a step took to ENQUEUE.
 // All activations the run keeps for backward live in ONE caller-allocated blob laid out by v100_ir_stack_plan; backward walks the
 // blocks in reverse with one shared workspace and two ping-pong gradient buffers.  Pure sequencing of v100_ir_fwd_train / v100_ir_bwd
-// (same kernels, same order, bit-identical results).
+// (same kernels, same order, bit-identical results) -- except that backward runs the wide blocks' 1x1 weight gradients later, several
+// blocks' in one grouped launch (stack_flush_plan; the same sums in the same order, bit-identical too).
 //
 // desc (HOST ints): {n, B, T, bf16, act16_level, want_last_shadow} then n x {cin, hid, cout, k, stride, residual}
 // plan (HOST long long out, 8 per block + 6): per block byte offsets into the blob of a1, a2, a3, y, y16 (or -1), coef, prep, T_out;
@@ -537,10 +577,14 @@ extern "C" int v100_ir_prep_batched(const int* shapes, const void* const* w1s, c
 // params (HOST pointer table, 18 per block): w1 g1 b1 rm1 rv1 nbt1 | wd g2 b2 rm2 rv2 nbt2 | w3 g3 b3 rm3 rv3 nbt3
 enum { ST_N, ST_B, ST_T, ST_BF16, ST_LEVEL, ST_SHADOW, ST_HDR };
 namespace {
-struct StackBlock { int sh[IR_NSHAPE]; long long a1, a2, a3, y, y16, coef, prep; int Tout; size_t grad_floats; };
+struct StackBlock { int sh[IR_NSHAPE]; long long a1, a2, a3, y, y16, coef, prep; int Tout; size_t grad_floats; long long defer_off; };
 inline size_t al256(size_t v) { return (v + 255) & ~size_t(255); }
+// the least tiles of a weight gradient that defers to a grouped launch (one XCD's 32 CUs: 8 such problems fill the chip)
+// and of a grouped flush (3/4 of the chip; below, split-K launches per problem are faster); v100_ir_stack_wgrad_group_thresholds
+int wg_min_problem_tiles = 32, wg_min_flush_tiles = 192;
 // fills blocks[0..n) and the totals; returns 0 on a bad descriptor
-int stack_layout(const int* desc, StackBlock* blk, size_t& blob_bytes, size_t& bwd_ws, size_t& grad_floats, size_t& fwd_ws_off) {
+int stack_layout(const int* desc, StackBlock* blk, size_t& blob_bytes, size_t& bwd_ws, size_t& grad_floats, size_t& fwd_ws_off,
+                 int min_tiles = wg_min_problem_tiles) {
     const int n = desc[ST_N], B = desc[ST_B], bf = desc[ST_BF16], level = desc[ST_LEVEL];
     if (n <= 0 || n > 32 || B <= 0 || desc[ST_T] <= 0 || (bf != 0 && bf != 1)) return 0;
     int T = desc[ST_T];
@@ -583,9 +627,68 @@ int stack_layout(const int* desc, StackBlock* blk, size_t& blob_bytes, size_t& b
     fwd_ws_off = off;
     blob_bytes = al256(off + fwd_ws) + 256;
     bwd_ws = al256(bws) + 2 * al256(dxmax) + 256;
+    // blocks whose weight gradients backward defers to a grouped launch: da3 / da1 in a region of their own behind the shared part
+    // (block 0 is sized for a caller that passes x16; without it the block stays on the per-block path and its region unused)
+    for (int i = 0; i < n; ++i) {
+        blk[i].defer_off = -1;
+        if (ir_wgrad_defer_ok(blk[i].sh, i == 0 || blk[i - 1].y16 >= 0, min_tiles)) {
+            blk[i].defer_off = (long long)bwd_ws;
+            bwd_ws += ir_defer_bytes(blk[i].sh);
+        }
+    }
     return 1;
 }
+
+// Where the backward walk (blocks n-1 .. 0) flushes the deferred gradients.  flush[i] = tiles flushed right after block i's
+// backward, > 0: one grouped launch, < 0: too few to fill the chip, the ordinary per-problem launches (0: no flush).  A flush
+// falls where the pending problems hold >= min_flush tiles and the next block would not fit into the same launch (it does not
+// defer, or would take the launch past one tile per CU or WG_GROUP_MAX problems), and where the walk leaves the stack.
+void stack_flush_plan(const StackBlock* blk, int n, bool have_x16, int min_flush, bool* defer, int* flush) {
+    int tiles = 0, count = 0;
+    for (int i = n - 1; i >= 0; --i) {
+        defer[i] = blk[i].defer_off >= 0 && (i > 0 || have_x16);
+        flush[i] = 0;
+        if (defer[i]) { tiles += ir_wgrad_defer_tiles(blk[i].sh); count += 2; }
+        if (!count) continue;
+        const bool next = i > 0 && blk[i - 1].defer_off >= 0 && (i > 1 || have_x16);
+        const bool fits = next && count + 2 <= 16 && tiles + ir_wgrad_defer_tiles(blk[i - 1].sh) <= 256;
+        if (i == 0 || count + 2 > 16 || (tiles >= min_flush && !fits)) {
+            flush[i] = tiles >= min_flush ? tiles : -tiles;
+            tiles = count = 0;
+        }
+    }
+}
 }   // namespace
+
+// Test hook: the least tiles of a gradient that defers (32) and of a grouped flush (192).  The defaults are what fills the chip;
+// tests lower them to reach the grouped path at small shapes.  Changes v100_ir_stack_plan's bwd_ws_bytes: set before planning.
+extern "C" int v100_ir_stack_wgrad_group_thresholds(int min_problem_tiles, int min_flush_tiles) {
+    if (min_problem_tiles < 1 || min_flush_tiles < 1) return V100_ERR_SHAPE;
+    wg_min_problem_tiles = min_problem_tiles;
+    wg_min_flush_tiles = min_flush_tiles;
+    return V100_OK;
+}
+
+// Host only (no GPU call): what v100_ir_stack_bwd does with the weight gradients of this descriptor at these thresholds.
+// out (HOST long longs, 3 per block + 2): {defers, byte offset of the block's region in the backward workspace (-1: none),
+// flush (see stack_flush_plan)}; then {bwd_ws_bytes, bytes of the shared part in front of the regions}.
+extern "C" int v100_ir_stack_wgrad_plan(const int* desc, int have_x16, int min_problem_tiles, int min_flush_tiles, long long* out) {
+    if (!desc || !out) return V100_ERR_NULL;
+    if (min_problem_tiles < 1 || min_flush_tiles < 1) return V100_ERR_SHAPE;
+    StackBlock blk[32];
+    size_t blob, bws, gf, fwo;
+    if (!stack_layout(desc, blk, blob, bws, gf, fwo, min_problem_tiles)) return V100_ERR_SHAPE;
+    const int n = desc[ST_N];
+    bool defer[32]; int flush[32];
+    stack_flush_plan(blk, n, have_x16 != 0, min_flush_tiles, defer, flush);
+    size_t shared = bws;
+    for (int i = 0; i < n; ++i) {
+        out[3 * i] = defer[i]; out[3 * i + 1] = blk[i].defer_off; out[3 * i + 2] = flush[i];
+        if (blk[i].defer_off >= 0 && (size_t)blk[i].defer_off < shared) shared = (size_t)blk[i].defer_off;
+    }
+    out[3 * n] = (long long)bws; out[3 * n + 1] = (long long)shared;
+    return V100_OK;
+}
 
 extern "C" long long v100_ir_stack_plan(const int* desc, long long* plan) {
     if (!desc || !plan) return -1;
@@ -673,9 +776,30 @@ extern "C" int v100_ir_stack_bwd(const int* desc, const void* const* params, con
                chan_bn3_bwd_fits(sh[IR_B], sh[IR_T]) && v100_ir_act16_supported(sh) &&
                dw_bwd_da1_supported(sh[IR_B], sh[IR_HID], sh[IR_T], sh[IR_K], v100_dw_num_groups(sh[IR_B], sh[IR_HID])) && sh[IR_ACT16] >= 2;
     };
+    // Deferred weight gradients (stack_flush_plan): the wide blocks' 1x1 weight gradients wait for one grouped launch, one tile per
+    // CU through the whole contraction, instead of a split-K launch + slab reduction each.  Same sums in the same order.
+    bool defer[32]; int flush[32];
+    stack_flush_plan(blk, n, x16 != nullptr, wg_min_flush_tiles, defer, flush);
+    const void* gp[5 * 16]; int gd[8 * 16]; int gblk[16]; int ng = 0;      // pending problems (v100_pw_wgrad_group's tables), their blocks
+    auto flush_pending = [&](bool grouped) -> int {
+        int rc = V100_OK;
+        if (grouped) rc = v100_pw_wgrad_group(ng, gp, gd, stream);
+        else
+            for (int j = 0; j < ng && rc == V100_OK; ++j) {                 // too few tiles: split-K per problem, slabs in the shared workspace
+                IrBwdWs w;
+                ir_bwd_carve(blk[gblk[j]].sh, w0, w);
+                const int* d = gd + 8 * j;
+                rc = v100_pw_wgrad_io(gp[5 * j], nullptr, nullptr, nullptr, nullptr, d[5], gp[5 * j + 1], (const float*)gp[5 * j + 2],
+                                      (const float*)gp[5 * j + 3], d[6], w.slab, (float*)const_cast<void*>(gp[5 * j + 4]), d[4], d[0], d[1], d[2], d[3],
+                                      d[7], stream);
+            }
+        ng = 0;
+        return rc;
+    };
     bool dy_is16 = false;
     for (int i = n - 1; i >= 0; --i) {
         StackBlock b = blk[i];
+        if (defer[i]) b.sh[IR_PREPPED] |= 64;
         // dx of block i is dy of block i - 1: 16-bit when both are capable blocks (with or without a residual)
         const bool dx_is16 = i > 0 && grad16_ok(i) && grad16_ok(i - 1);
         if (dy_is16 && !grad16_ok(i)) return V100_ERR_SHAPE;      // (cannot happen: dy_is16 was decided with this block's capability)
@@ -684,7 +808,8 @@ extern "C" int v100_ir_stack_bwd(const int* desc, const void* const* params, con
         float* g = (float*)grads + goff;
         const int cin = b.sh[IR_CIN], hid = b.sh[IR_HID], cout = b.sh[IR_COUT], k = b.sh[IR_K];
         void* dxi = i > 0 ? (void*)pp[i & 1] : dx;
-        const void* P[25];
+        const void* P[26];
+        P[25] = defer[i] ? w0 + b.defer_off : nullptr;
         P[0] = i > 0 ? (const void*)(base + blk[i - 1].y) : x;
         P[1] = base + b.a1; P[2] = base + b.a2; P[3] = base + b.a3;
         P[4] = params[18 * i + 0]; P[5] = params[18 * i + 6]; P[6] = params[18 * i + 12];
@@ -697,6 +822,21 @@ extern "C" int v100_ir_stack_bwd(const int* desc, const void* const* params, con
         P[22] = w0; P[23] = base + b.prep;
         P[24] = i > 0 ? (blk[i - 1].y16 >= 0 ? (const void*)(base + blk[i - 1].y16) : nullptr) : x16;
         CK(v100_ir_bwd(b.sh, P, stream));
+        if (defer[i]) {
+            const int B = b.sh[IR_B], T = b.sh[IR_T], mc = hid > cout ? hid : cout;
+            const float* coef = (const float*)(base + b.coef);
+            const char* own = w0 + b.defer_off;
+            // project gradient: dW3 = da3 x relu6(s2 a2 + t2); expand gradient: dW1 = da1 x (shadow of the block input)
+            const void* pr[2][5] = {{own, P[2], coef + 4 * mc, coef + 5 * mc, P[19]}, {own + ir_defer_da3_bytes(b.sh), P[24], nullptr, nullptr, P[13]}};
+            const int dm[2][8] = {{B, cout, hid, T, v100_pw_wgrad_splits(B, cout, hid), 0, 1, WG_IO_G | WG_IO_X},
+                                  {B, hid, cin, T, v100_pw_wgrad_splits(B, hid, cin), 0, 0, WG_IO_G | WG_IO_X}};
+            for (int j = 0; j < 2; ++j, ++ng) {
+                for (int e = 0; e < 5; ++e) gp[5 * ng + e] = pr[j][e];
+                for (int e = 0; e < 8; ++e) gd[8 * ng + e] = dm[j][e];
+                gblk[ng] = i;
+            }
+        }
+        if (flush[i]) CK(flush_pending(flush[i] > 0));
         dyi = dxi;
         dy_is16 = dx_is16;
     }

@@ -8,8 +8,13 @@
 // waves 8-11 stage the TRANSFORMED operand's 128 x 64 tile (BatchNorm-backward affine of two bf16 tensors, or BatchNorm + ReLU6):
 // NSQ register stages of loads, transform, bf16 pack, 4 ds_write_b128 per lane and step.  One barrier per step.  Full tiles only
 // (M % GR == 0, K % XR == 0); TAIL: T % 64 != 0, contraction indices past T are zeroed in BOTH operands (masks on the plain one).
-template <int GM, int XM, bool TAIL, int IO, int GR, int XR, int NSW>
-__global__ __launch_bounds__(512 + 64 * NSW) void pw_wgrad_bf16_ws_kernel(WgParams p) {
+// GRP (pointwise_bf16_wgrad_group.h): the workgroup walks the WHOLE contraction of its tile in the order of the p.S splits and sums
+// the splits' partial tiles itself, in slab order from 0.f (pw_slab_reduce4_kernel's sum, bit for bit); p.partial is then the
+// finished [M][K] gradient.  The running sum's fragments live in registers, the last RL of the four in LDS (runs: one f32x4 per
+// matrix lane and register quad, [RL * 4][512]).
+template <int GM, int XM, bool TAIL, int IO, int GR, int XR, int NSW, bool GRP = false, int RL = 0>
+__device__ __forceinline__ void pw_wgrad_bf16_ws_body(const WgParams& p, const int s, const int mt, const int ktile, unsigned char* const As0,
+                                                      unsigned char* const Bs0, f32x4* const runs) {
     // (both plain -- G = the finished gradient da1, round 5 --: G takes the 128-row side and its "transform" is a copy)
     static_assert(!(GM != PW_X_NONE && XM != PW_X_NONE), "at most one transformed operand (128 rows); the other one plain (256 rows)");
     static_assert((IO & WG_IO_G) && (IO & WG_IO_X) && (GM != PW_X_AFFINE2 || (IO & WG_IO_G2)), "bf16-stored operands only");
@@ -21,17 +26,15 @@ __global__ __launch_bounds__(512 + 64 * NSW) void pw_wgrad_bf16_ws_kernel(WgPara
     constexpr int NSQ = (QM == PW_X_AFFINE2 && NSW == 4) ? 3 : 4;    // register stages of the transformed operand
     constexpr int NQP = 16 / NSW;                           // 16-byte pieces per staging lane and step
     constexpr int QRS = 8 * NSW;                            // rows between a lane's pieces
-    __shared__ __attribute__((aligned(16))) unsigned char As[2][GR * 128];   // [m][t] bf16
-    __shared__ __attribute__((aligned(16))) unsigned char Bs[2][XR * 128];   // [k][t] bf16
+    unsigned char (*As)[GR * 128] = reinterpret_cast<unsigned char (*)[GR * 128]>(As0);   // [2][m][t] bf16
+    unsigned char (*Bs)[XR * 128] = reinterpret_cast<unsigned char (*)[XR * 128]>(Bs0);   // [2][k][t] bf16
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int s, mt, ktile;
-    wg_work(p, s, mt, ktile);
     const int m0 = mt * GR, n0 = ktile * XR;
     const int M = p.M, K = p.K, T = p.T;
     const int P16 = pw_pitch16(T, p.B);
     const int nt = (T + BF_BK - 1) / BF_BK;
-    const WgSpan sp = wg_span(p, s, nt);
+    const WgSpan sp = GRP ? WgSpan{0, p.B, 0, nt} : wg_span(p, s, nt);       // GRP: the splits' utterance runs, one behind the other
     const int nsteps = sp.nb * sp.ntl, b_lo = sp.b_lo;
     // step -> (batch element, t offset); steps past the end are clamped to the last (an unconditional, redundant load: a
     // conditional one would make hipcc wait for the YOUNGER stage at the join)
@@ -44,11 +47,12 @@ __global__ __launch_bounds__(512 + 64 * NSW) void pw_wgrad_bf16_ws_kernel(WgPara
     };
     // contraction indices t0 + 8 ch + e >= T of a 16-byte piece -> zero
     auto tail_mask = [&](u32x4 v, int tb) {
+        const int nv = T - tb;                              // (one live value, constants compared against it: registers are short in GRP)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] &= (tb + 2 * j < T ? 0xffffu : 0u) | (tb + 2 * j + 1 < T ? 0xffff0000u : 0u);
+        for (int j = 0; j < 4; ++j) v[j] &= nv > 2 * j + 1 ? 0xffffffffu : (nv > 2 * j ? 0xffffu : 0u);
         return v;
     };
-    if (nsteps == 0) {                                      // (no work for this split: the partial tile is zeros)
+    if (!GRP && nsteps == 0) {                              // (no work for this split: the partial tile is zeros)
         if (wave < 8) {
             const int wm = wave / NX, wn = wave % NX, col = lane & 31, half = lane >> 5;
 #pragma unroll
@@ -257,15 +261,63 @@ __global__ __launch_bounds__(512 + 64 * NSW) void pw_wgrad_bf16_ws_kernel(WgPara
     for (int i = 0; i < 4; ++i) { *reinterpret_cast<u32x4*>(Ps[0] + ldsP + i * 8192) = piece_out(0, rp[0][i]); load_p(2, S0{}, i); }
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();                                       // step 0 is in LDS
+    // GRP: behind the last step of a split the partial tile joins the running sum and the accumulators restart from zero.  The
+    // splits of wg_span, one behind the other, ARE the walk b-major, t-minor: S <= B ends one every ceil(B / S) utterances (the last
+    // may be short, later ones empty), S = B * TS at the ends hi(c) = (c + 1) nt / TS of every utterance's chunks (some empty when
+    // nt < TS).  An empty split's slab is zeros and changes no sum.
+    constexpr int NRR = GRP ? 4 - RL : 1;                  // running-sum fragments in registers
+    f32x16 run[NRR];
+    const int per = ((p.B + p.S - 1) / p.S) * sp.ntl, TS = p.S > p.B ? p.S / p.B : 0;
+    auto next_fold = [&](int cur) {                        // the first split end behind step cur (wave-uniform)
+        if (TS == 0) return min(cur + per, nsteps);
+        const int b = cur / sp.ntl, w = cur - b * sp.ntl;
+        int c = 0;
+        while ((int)((long)(c + 1) * sp.ntl / TS) <= w) ++c;
+        return b * sp.ntl + (int)((long)(c + 1) * sp.ntl / TS);
+    };
+    int fold_at = GRP ? next_fold(0) : 0;
+    if constexpr (GRP) {
+#pragma unroll
+        for (int f = 0; f < NRR; ++f)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) run[f][r] = 0.f;
+#pragma unroll
+        for (int f = 0; f < RL * 4; ++f) runs[f * 512 + tid] = f32x4{0.f, 0.f, 0.f, 0.f};    // (a lane's own slots: no barrier)
+    }
+    auto fold = [&](int done) {
+        if constexpr (GRP) {
+            if (done != fold_at) return;
+            fold_at = next_fold(done);
+#pragma unroll
+            for (int f = 0; f < 4; ++f) {
+                f32x16& a = acc[f >> 1][f & 1];
+                if (f < NRR) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) run[f < NRR ? f : 0][r] += a[r];
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        f32x4& d = runs[((f - NRR) * 4 + q) * 512 + tid];
+                        d += f32x4{a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]};
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) a[r] = 0.f;
+            }
+        }
+    };
     int st = 0;
     for (; st + 1 < nsteps; st += 2) {                     // pairs, then the odd step
         block(st, S1{});
+        fold(st + 1);
         __syncthreads();
         block(st + 1, S0{});
+        fold(st + 2);
         __syncthreads();
     }
     if (st < nsteps) {
         block(st, S1{});
+        fold(st + 1);
         __syncthreads();
     }
     const int col = lane & 31, half = lane >> 5;
@@ -277,6 +329,20 @@ __global__ __launch_bounds__(512 + 64 * NSW) void pw_wgrad_bf16_ws_kernel(WgPara
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
                 const int k = n0 + wn * 64 + j * 32 + col;
-                p.partial[((size_t)s * M + m) * K + k] = acc[i][j][r];      // (full tiles only: no bounds tests, no exec-mask branches)
+                float v = acc[i][j][r];
+                if constexpr (GRP) {
+                    const int f = i * 2 + j;
+                    v = f < NRR ? run[f < NRR ? f : 0][r] : runs[((f - NRR) * 4 + (r >> 2)) * 512 + tid][r & 3];
+                }
+                p.partial[((size_t)s * M + m) * K + k] = v;      // (full tiles only: no bounds tests, no exec-mask branches)
             }
+}
+
+template <int GM, int XM, bool TAIL, int IO, int GR, int XR, int NSW>
+__global__ __launch_bounds__(512 + 64 * NSW) void pw_wgrad_bf16_ws_kernel(WgParams p) {
+    __shared__ __attribute__((aligned(16))) unsigned char As[2][GR * 128];   // [m][t] bf16
+    __shared__ __attribute__((aligned(16))) unsigned char Bs[2][XR * 128];   // [k][t] bf16
+    int s, mt, ktile;
+    wg_work(p, s, mt, ktile);
+    pw_wgrad_bf16_ws_body<GM, XM, TAIL, IO, GR, XR, NSW>(p, s, mt, ktile, &As[0][0], &Bs[0][0], nullptr);
 }

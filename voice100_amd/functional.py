@@ -363,6 +363,14 @@ def set_stack_segment(n: Optional[int]) -> None:
     _STACK_SEGMENT = n
 
 
+def set_wgrad_group_thresholds(min_problem_tiles: int = 32, min_flush_tiles: int = 192) -> None:
+    """Least tiles of a 1x1 weight gradient the stack executor defers, and of a grouped flush (v100_ir_stack_wgrad_group_thresholds).
+    The defaults fill the chip; tests lower them to reach the grouped launch at small shapes.  The backward workspace is planned with
+    them, so the cached plans go."""
+    N.call("v100_ir_stack_wgrad_group_thresholds", int(min_problem_tiles), int(min_flush_tiles))
+    _STACK_PLANS.clear()
+
+
 def _stack_plan(cfgs, B, T, bf16, level, last_shadow):
     """(desc ctypes array, per-block offsets, totals) of a run of blocks at this input shape: computed once per distinct key."""
     key = (cfgs, B, T, bf16, level, last_shadow)
