@@ -623,6 +623,22 @@ int v100_world_unnormalize_v2(const float* x, float* f0, float* logspc, float* c
                               const float* ls_mean, const float* ls_std, const float* ca_mean, const float* ca_std,
                               int B, int T, int S, int Cap, void* stream);
 
+/* ---- K22 the phone head's masked cross-entropy of AlignTextToAudioMultiTaskModel (voice100/models/tts.py:328-331; csrc/phone_loss.hip),
+ * value + gradient in one pass.  logits [B][V][L] fp32, channel first as the 1x1 head writes them; target [B][L] int64;
+ * target_len [B] int32.  Column (b, l) counts iff l < min(max(target_len[b], 0), L):
+ *   loss[0] = sum over counted columns of (logsumexp_v logits[b][:][l] - logits[b][target][l]) / sum_b clamp(target_len[b], 0, L)
+ *   unit [B][V][L] = d loss / d logits for a unit upstream gradient = (softmax - onehot) / that sum, 0 in every other column.
+ * torch's CrossEntropyLoss semantics: target == -100 (ignore_index) adds no loss and has a zero gradient but still counts in the
+ * divisor when inside the length; every length 0 gives 0 / 0 = NaN.  Any other target outside [0, V) (torch raises) is never used
+ * as an index: that column's loss is NaN.  Columns that do not count are never loaded.  partial: v100_masked_ce_parts(B, L)
+ * floats (one per workgroup of 64 columns; -1 on B or L < 1), added in block order by a second launch: no atomics, bit-identical
+ * from call to call.  1 on B, V or L < 1; 3 on a NULL pointer. */
+int v100_masked_ce_parts(int B, int L);
+int v100_masked_ce(const float* logits, const long long* target, const int* target_len, float* partial, float* loss, float* unit,
+                   int B, int V, int L, void* stream);
+/* dlogits = unit * gout[0], gout [1] on the device */
+int v100_masked_ce_bwd(const float* unit, const float* gout, float* dlogits, int B, int V, int L, void* stream);
+
 /* ---- sample-rate conversion (csrc/resample.hip): torchaudio.functional.resample's default method ("sinc_interpolation", Hann
  * window) for a rate pair reduced to o / n (orig / gcd, new / gcd).  An utterance of len samples gives
  * v100_resample_out_len(len, o, n) = ceil(n len / o) outputs (a HOST helper, 64-bit: 2^31 - 1 samples at 16 -> 22.05 kHz pass

@@ -557,8 +557,8 @@ static inline DwPathConfig dw_path_config() {
     return cfg;
 }
 
-// kernel sizes used by the reference's networks: asr.py:68-76, tts.py:18-25, 73-76
-#define V100_DW_SPECIALISED(X) X(5) X(7) X(11) X(17) X(19) X(27) X(29) X(33) X(35) X(51) X(59) X(65) X(67) X(75) X(83)
+// kernel sizes used by the reference's networks: asr.py:68-76, tts.py:18-25, 37-46 (47: the multi-task decoder only), 73-76
+#define V100_DW_SPECIALISED(X) X(5) X(7) X(11) X(17) X(19) X(27) X(29) X(33) X(35) X(47) X(51) X(59) X(65) X(67) X(75) X(83)
 
 // One launcher per (input mode, output mode) pair, each in its own translation unit (they compile
 // in parallel).  Returns false when (K, stride) has no specialisation.

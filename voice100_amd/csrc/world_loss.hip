@@ -8,6 +8,7 @@
 // targets once, forms the four loss terms, and writes the frame's gradient for unit upstream gradients straight away;
 // per-block partial sums go to a slab that one small kernel reduces in a fixed order (deterministic, no atomics).
 #include "common.h"
+#include "loss_common.h"
 #include <math.h>
 
 struct WorldLossParams {
@@ -27,13 +28,6 @@ struct WorldLossParams {
 __device__ __forceinline__ void wl_el(bool l1, float d, float& v, float& g) {
     if (l1) { v = fabsf(d); g = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
     else { v = d * d; g = 2.f * d; }
-}
-
-// sum over b of clamp(length[b], 0, n): the number of unmasked frames (torch.sum(mask), _layers_v1.py:80,88-92)
-__device__ __forceinline__ float wl_mask_sum(const int* __restrict__ length, int B, int n, int lane) {
-    float s = 0.f;
-    for (int b = lane; b < B; b += 64) s += (float)min(max(length[b], 0), n);
-    return wave_sum(s);
 }
 
 __global__ __launch_bounds__(256) void world_loss_kernel(WorldLossParams p) {
@@ -348,11 +342,6 @@ __global__ __launch_bounds__(256) void align_loss_finalize_kernel(const float* _
     const float ms = wl_mask_sum(text_len, B, L, lane);
     __syncthreads();
     if (threadIdx.x == 0) loss[0] = ((red[0] + red[1]) + (red[2] + red[3])) / ms;
-}
-
-__global__ void scale_by_scalar_kernel(const float* __restrict__ unit, const float* __restrict__ gout, float* __restrict__ dpred, long total) {
-    const float g = gout[0];
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) dpred[i] = unit[i] * g;
 }
 
 extern "C" int v100_align_loss_parts(int B, int L) { return (int)(((long)B * L + 255) / 256); }

@@ -1518,6 +1518,66 @@ def align_loss(pred_bl2, align, text_len):
     return AlignLossFn.apply(pred_bl2, align, text_len)
 
 
+class MaskedCrossEntropyFn(torch.autograd.Function):
+    """K22, the phone head's loss of AlignTextToAudioMultiTaskModel (tts.py:328-331): CrossEntropyLoss(reduction='none') on the
+    channel-first logits [B, V, L], masked by target_len and divided by the mask sum -- value and gradient in one HIP pass
+    (v100_masked_ce); backward scales the saved unit gradient (v100_masked_ce_bwd)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, target_len):
+        _check(logits, "masked_cross_entropy")
+        logits = logits.contiguous()
+        B, V, L = logits.shape
+        dev = logits.device
+        target = target.to(device=dev, dtype=torch.int64).contiguous()
+        target_len = target_len.to(device=dev, dtype=torch.int32).contiguous()
+        if CHECK_IDS and target.numel():
+            _check_ids(torch.where(target == -100, torch.zeros_like(target), target), V, "masked_cross_entropy targets")
+        parts = N.helper("v100_masked_ce_parts", B, L)
+        if parts < 0:
+            raise RuntimeError(f"masked_cross_entropy: invalid shape {list(logits.shape)}")
+        partial = _f32(parts, like=logits)
+        loss = _f32(1, like=logits)
+        unit = torch.empty_like(logits)
+        N.call("v100_masked_ce", logits, target, target_len, partial, loss, unit, B, V, L)
+        ctx.save_for_backward(unit)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        (unit,) = ctx.saved_tensors
+        B, V, L = unit.shape
+        dlogits = torch.empty_like(unit)
+        N.call("v100_masked_ce_bwd", unit, gout.to(torch.float32).reshape(1).contiguous(), dlogits, B, V, L)
+        return dlogits, None, None
+
+
+def _masked_cross_entropy_stock(logits_bvl, target, target_len):
+    """The three lines of tts.py:328-331 in stock ops (CPU tensors and graph recording)."""
+    ce = torch.nn.functional.cross_entropy(logits_bvl, target, reduction="none")                 # [B, L]
+    mask = (torch.arange(target.shape[1], device=target.device)[None, :] < target_len.to(target.device)[:, None]).to(ce.dtype)
+    return torch.sum(ce * mask) / torch.sum(mask)
+
+
+def masked_cross_entropy(logits_bvl, target, target_len):
+    """logits [B, V, L] fp32 (channel first, as the 1x1 head writes them), target [B, L] int64, target_len [B] -> 0-dim loss
+    = sum over l < target_len[b] of the cross-entropy / sum_b clamp(target_len[b], 0, L).  torch's semantics: a target of -100 is
+    ignored but counted in the divisor; every length 0 gives 0 / 0 = NaN (the reference's value; not special-cased).  A target width
+    other than L raises RuntimeError, as the reference's CrossEntropyLoss does.  On CPU tensors, or while a graph is recorded, the
+    stock-op restatement runs; on the GPU one fused HIP pass (K22), where any other target outside [0, V) makes the loss NaN instead
+    of faulting (VOICE100_CHECK_IDS=1: IndexError before the launch, as the reference raises)."""
+    if logits_bvl.dim() != 3 or target.dim() != 2 or target_len.dim() != 1:
+        raise RuntimeError("masked_cross_entropy: logits [B, V, L], target [B, L], target_len [B] expected")
+    B, V, L = logits_bvl.shape
+    if target.shape[0] != B or target.shape[1] != L or target_len.shape[0] != B:
+        raise RuntimeError(f"masked_cross_entropy: logits {list(logits_bvl.shape)} need target [{B}, {L}] and target_len [{B}], got "
+                           f"{list(target.shape)} and {list(target_len.shape)}")
+    from ._base import tracing
+    if not logits_bvl.is_cuda or tracing():
+        return _masked_cross_entropy_stock(logits_bvl, target, target_len)
+    return MaskedCrossEntropyFn.apply(logits_bvl, target, target_len)
+
+
 class CTCLossFn(torch.autograd.Function):
     """log_softmax(dim=-1) + CTCLoss(blank=0, reduction='mean', zero_infinity=True) on logits [B, T, V]
     (asr.py:146-152), forward and gradient in one pass of the HIP lattice kernels.  Limits of the kernel: V <= 128 classes,

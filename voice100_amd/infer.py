@@ -120,7 +120,9 @@ class TTSPipeline:
           -> ap = decode_aperiodicity(codeap); waveform = synthesize(f0, spc, ap)                      (vocoder.py:100-101; round 4,
                                                            csrc/world.hip -- parity unpinned, see voice100_amd/vocoder.py)
 
-    configs[2] therefore ends in a waveform [B, samples] on the device ("wave", zero beyond each utterance's "wave_len")."""
+    configs[2] therefore ends in a waveform [B, samples] on the device ("wave", zero beyond each utterance's "wave_len").
+    An audio model whose predict returns a fourth value (AlignTextToAudioMultiTaskModel: the phone logits [B, Vt, La], tts.py:308-317)
+    gets it back as "phone_logits"; every other entry is what the three-value models give."""
 
     def __init__(self, align_model, audio_model, vocoder=None, head: int = 5, tail: int = 5, synthesize: bool = True,
                  f0_ceil: float = 1000.0):
@@ -136,7 +138,10 @@ class TTSPipeline:
         aligntext, at_len = align_expand(text, align, text_len, self.head, self.tail)
         # (align_expand sizes the batch exactly as wide as its longest utterance -- pad_sequence semantics, update_samples.py:66 --
         # so that one ends at the convolutions' zero padding, not at extra blank tokens)
-        f0, feat, codeap = self.audio_model.predict(aligntext)               # 2 * La - 1 frames
+        # 2 * La - 1 frames; AlignTextToAudioMultiTaskModel.predict adds the phone logits [B, Vt, La] as a fourth value (tts.py:308-317)
+        f0, feat, codeap, *extra = self.audio_model.predict(aligntext)
+        if len(extra) > 1:
+            raise RuntimeError(f"TTSPipeline: audio_model.predict returned {3 + len(extra)} values; three or four expected")
         v = self.vocoder
         if v is not None and v.use_mcep:
             B, T, C = feat.shape
@@ -148,6 +153,8 @@ class TTSPipeline:
         frames = torch.clamp_min(2 * at_len - 1, 0)
         out = {"align": align, "aligntext": aligntext, "aligntext_len": at_len, "f0": f0, "logspc": logspc, "spc": spc,
                "codeap": codeap, "frames": frames}
+        if extra:
+            out["phone_logits"] = extra[0]
         if v is not None and self.synthesize and v.n_fft == 512 and f0.shape[1] >= 2:
             wave, npulses = v.synthesize(f0, spc, frames=frames, f0_ceil=self.f0_ceil, codeap=codeap)
             out["wave"], out["n_pulses"] = wave, npulses

@@ -1,5 +1,5 @@
-"""TTS side of the hot path: VoiceDecoder, TextToAlignTextModel, AlignTextToAudioModel and the
-WORLD feature norm / loss glue.  Drop-in for voice100/models/tts.py:13-262 and
+"""TTS side of the hot path: VoiceDecoder, TextToAlignTextModel, AlignTextToAudioModel, the multi-task pair VoiceMultiTaskDecoder /
+AlignTextToAudioMultiTaskModel and the WORLD feature norm / loss glue.  Drop-in for voice100/models/tts.py:13-383 and
 voice100/models/_layers_v1.py:14-138 (same class names, constructor arguments, forward layouts and
 state_dict keys); the convolution stacks, the transposed convolution and the predict epilogue run
 on the MI355X kernels.
@@ -15,8 +15,8 @@ from . import functional as F_
 from ._base import Voice100ModelBase, tracing
 from .layers import InvertedResidual, PointwiseConv1d
 
-__all__ = ["VoiceDecoder", "TextToAlignTextModel", "AlignTextToAudioModel", "WORLDNorm", "WORLDLoss",
-           "generate_padding_mask", "adjust_size"]
+__all__ = ["VoiceDecoder", "VoiceMultiTaskDecoder", "TextToAlignTextModel", "AlignTextToAudioModel",
+           "AlignTextToAudioMultiTaskModel", "WORLDNorm", "WORLDLoss", "generate_padding_mask", "adjust_size"]
 
 
 def generate_padding_mask(x: torch.Tensor, length: torch.Tensor) -> torch.Tensor:
@@ -69,6 +69,53 @@ class VoiceDecoder(nn.Module):
             x = F_.ir_stack_train(self.layers[5:8], x)
             return self.layers[8](x)
         return self.layers(x)
+
+
+class VoiceMultiTaskDecoder(nn.Module):
+    """layer1: 6 IR @H (k=65,47,33,17,11,7); layer2: ConvTranspose1d(H, H/2, k5 s2 p2) -> 2 IR @H/2 (k=11,7) -> 1x1 to out_channels;
+    layer3: 1x1 from layer1's output to secondary_channels (tts.py:32-54).  [B, H, L] -> ([B, out_channels, 2L-1],
+    [B, secondary_channels, L]).  layer1's output feeds both branches, so its gradient is the sum of theirs: autograd adds the two
+    fp32 gradients before the stack's backward runs, which takes the gradient entering a stack as fp32 at every storage level."""
+
+    def __init__(self, hidden_size, out_channels, secondary_channels) -> None:
+        super().__init__()
+        half = hidden_size // 2
+        self.layer1 = nn.Sequential(
+            InvertedResidual(hidden_size, hidden_size, kernel_size=65),
+            InvertedResidual(hidden_size, hidden_size, kernel_size=47),
+            InvertedResidual(hidden_size, hidden_size, kernel_size=33),
+            InvertedResidual(hidden_size, hidden_size, kernel_size=17),
+            InvertedResidual(hidden_size, hidden_size, kernel_size=11),
+            InvertedResidual(hidden_size, hidden_size, kernel_size=7))
+        self.layer2 = nn.Sequential(
+            ConvTranspose1d(hidden_size, half, kernel_size=5, padding=2, stride=2),
+            InvertedResidual(half, half, kernel_size=11),
+            InvertedResidual(half, half, kernel_size=7),
+            PointwiseConv1d(half, out_channels, bias=True))
+        self.layer3 = PointwiseConv1d(hidden_size, secondary_channels, bias=True)
+
+    def forward(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        if tracing() or not x.is_cuda:
+            return self._stock_forward(x)
+        if self.training:
+            # 6 blocks | head 3 and the transposed conv, both on the stack's output | 2 blocks | head 2
+            x = F_.ir_stack_train(self.layer1[0:6], x)
+            y = self.layer3(x)
+            x = self.layer2[0](x)
+            x = F_.ir_stack_train(self.layer2[1:3], x)
+            return self.layer2[3](x), y
+        x = self.layer1(x)
+        return self.layer2(x), self.layer3(x)
+
+    def _stock_forward(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The reference's nn.Sequential in stock ops on the module's own parameters: graph recording and CPU tensors."""
+        for blk in self.layer1:
+            x = _stock.inverted_residual(blk, x)
+        y = _stock.pointwise_conv1d(self.layer3, x)
+        x = _stock.conv_transpose1d(self.layer2[0], x)
+        x = _stock.inverted_residual(self.layer2[1], x)
+        x = _stock.inverted_residual(self.layer2[2], x)
+        return _stock.pointwise_conv1d(self.layer2[3], x), y
 
 
 class WORLDLoss(nn.Module):
@@ -315,6 +362,116 @@ class AlignTextToAudioModel(Voice100ModelBase):
     def from_argparse_args(args, **kwargs):
         model = AlignTextToAudioModel(hidden_size=args.hidden_size, learning_rate=args.learning_rate,
                                       use_mcep=args.vocoder == "world_mcep", **kwargs)
+        if not args.resume_from_checkpoint:
+            if args.audio_stat is None:
+                args.audio_stat = f"./data/{args.dataset}-stat.pt"
+            model.norm.load_state_dict(torch.load(args.audio_stat))
+        return model
+
+
+class AlignTextToAudioMultiTaskModel(Voice100ModelBase):
+    """aligned text [B, L] int64 -> WORLD features at 2L-1 frames AND phone logits [B, target_vocab_size, L] from the decoder's
+    second head (tts.py:265-383, the README's "CMU multi-task model").
+
+    One departure from the reference: the criterion is built as WORLDLoss(use_mel_weights=not use_mcep, sample_rate, n_fft), what
+    AlignTextToAudioModel does (tts.py:170).  The reference passes `use_logspc_weights=`, a keyword its WORLDLoss does not have
+    (tts.py:284 against _layers_v1.py:38-46), so its constructor raises TypeError; `use_mel_weights` is what the misspelt keyword
+    evidently meant.
+
+    On the GPU the decoder runs once, WORLDLoss.fused (K12) takes its first output and functional.masked_cross_entropy (K22) its
+    second: nothing is split, masked or reduced in torch.  On CPU tensors, or while a graph is recorded, the stock-op restatement
+    of the same arithmetic runs."""
+
+    def __init__(self, vocab_size: int, target_vocab_size: int, hidden_size: int, learning_rate: float = 1e-3,
+                 use_mcep: bool = False) -> None:
+        super().__init__()
+        self.save_hyperparameters()
+        self.hidden_size = hidden_size
+        self.vocab_size = vocab_size
+        self.target_vocab_size = target_vocab_size
+        self.sample_rate = 16000
+        self.n_fft = 512
+        self.hasf0_size = 1
+        self.f0_size = 1
+        self.logspc_size = 25 if use_mcep else self.n_fft // 2 + 1
+        self.codeap_size = 1
+        self.embedding = nn.Embedding(vocab_size, hidden_size)
+        self.audio_size = self.hasf0_size + self.f0_size + self.logspc_size + self.codeap_size
+        self.decoder = VoiceMultiTaskDecoder(hidden_size, self.audio_size, self.target_vocab_size)
+        self.norm = WORLDNorm(self.logspc_size, self.codeap_size)
+        self.criterion = WORLDLoss(use_mel_weights=not use_mcep, sample_rate=self.sample_rate, n_fft=self.n_fft)
+        self.target_criterion = nn.CrossEntropyLoss(reduction="none")     # the reference's attribute; no parameters, no state
+
+    def _stock_path(self, aligntext: torch.Tensor) -> bool:
+        return tracing() or not aligntext.is_cuda
+
+    def _decode(self, aligntext: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """([B, 2L-1, A], [B, Vt, L])"""
+        if self._stock_path(aligntext):
+            x, y = self.decoder(_stock.embedding_bct(aligntext, self.embedding.weight))
+            return torch.transpose(x, 1, 2), y
+        x = F_.embedding_bct(aligntext, self.embedding.weight)   # [B, H, L]
+        x, y = self.decoder(x)                                   # [B, A, 2L-1], [B, Vt, L]
+        return F_.transpose_last2(x), y
+
+    def forward(self, aligntext: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        x, target_logits = self._decode(aligntext)
+        hasf0_logits, f0_hat, logspc_hat, codeap_hat = torch.split(
+            x, [self.hasf0_size, self.f0_size, self.logspc_size, self.codeap_size], dim=2)
+        return hasf0_logits[:, :, 0], f0_hat[:, :, 0], logspc_hat, codeap_hat, target_logits
+
+    @torch.no_grad()
+    def predict(self, aligntext: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        x, logits = self._decode(aligntext)
+        n = self.norm
+        if self._stock_path(aligntext):
+            sizes = [self.hasf0_size, self.f0_size, self.logspc_size, self.codeap_size]
+            return _stock.world_unnormalize_gate(x, n, sizes) + (logits,)
+        return F_.world_unnormalize_gate(x, n.f0_mean, n.f0_std, n.logspc_mean, n.logspc_std, n.codeap_mean, n.codeap_std) + (logits,)
+
+    def _calc_batch_loss(self, batch):
+        (f0, f0_len, logspc, codeap), (aligntext, aligntext_len), (phonetext, phonetext_len) = batch
+        x, target_logits = self._decode(aligntext)
+        if phonetext.dim() != 2 or phonetext.shape[1] != target_logits.shape[2]:
+            raise RuntimeError(f"phonetext {list(phonetext.shape)} does not match the phone logits {list(target_logits.shape)} "
+                               "(one target per aligned-text position)")
+        if self._stock_path(aligntext):
+            hasf0 = (f0 >= 30.0).to(torch.float32)                # tts.py:321-327
+            f0, logspc, codeap = self.norm.normalize(f0, logspc, codeap)
+            hasf0_logits, f0_hat, logspc_hat, codeap_hat = torch.split(
+                x, [self.hasf0_size, self.f0_size, self.logspc_size, self.codeap_size], dim=2)
+            world = self.criterion(f0_len, hasf0_logits[:, :, 0], f0_hat[:, :, 0], logspc_hat, codeap_hat, hasf0, f0, logspc, codeap)
+        else:
+            world = self.criterion.fused(f0_len, x, f0, logspc, codeap, self.norm)
+        return tuple(world) + (F_.masked_cross_entropy(target_logits, phonetext, phonetext_len),)
+
+    def _step(self, task: str, batch) -> torch.Tensor:
+        hasf0_loss, f0_loss, logspc_loss, codeap_loss, phone_loss = self._calc_batch_loss(batch)
+        loss = hasf0_loss + f0_loss + logspc_loss + codeap_loss + phone_loss
+        self.log(f"{task}_loss", loss)                           # tts.py:351-357
+        self.log(f"{task}_hasf0_loss", hasf0_loss)
+        self.log(f"{task}_f0_loss", f0_loss)
+        self.log(f"{task}_logspc_loss", logspc_loss)
+        self.log(f"{task}_codeap_loss", codeap_loss)
+        self.log(f"{task}_phone_loss", phone_loss)
+        return loss
+
+    def training_step(self, batch, batch_idx=0) -> torch.Tensor:
+        return self._step("train", batch)
+
+    def validation_step(self, batch, batch_idx=0):
+        return {"val_loss": self._step("val", batch)}
+
+    def test_step(self, batch, batch_idx=0):
+        return {"test_loss": self._step("test", batch)}
+
+    configure_optimizers = AlignTextToAudioModel.configure_optimizers
+    add_model_specific_args = staticmethod(AlignTextToAudioModel.add_model_specific_args)
+
+    @staticmethod
+    def from_argparse_args(args, **kwargs):
+        model = AlignTextToAudioMultiTaskModel(hidden_size=args.hidden_size, learning_rate=args.learning_rate,
+                                               use_mcep=args.vocoder == "world_mcep", **kwargs)
         if not args.resume_from_checkpoint:
             if args.audio_stat is None:
                 args.audio_stat = f"./data/{args.dataset}-stat.pt"
