@@ -509,6 +509,19 @@ long long v100_ctc_align_workspace_bytes(int B, int T, int Lmax);
 int v100_ctc_align_block(void);
 int v100_ctc_align(const float* logp, const long long* labels, const int* in_len, const int* lab_len, void* moves_ws, int* path,
                    long long* best_labels, int* align, float* score, int B, int T, int V, int Lmax, int max_move, void* stream);
+/* K23, batched edit distance (csrc/edit_distance.hip): the Levenshtein distance (unit costs for substitution, insertion and
+ * deletion) between hyp [B][Th] int64 and ref [B][Tr] int64, rows of hyp_len / ref_len [B] int32 ids (clamped to [0, width] on the
+ * device; nothing beyond a row's length is read; ids compare on all 64 bits).  levels: 1 = id level (a token is one id), 2 = word
+ * level (a token is a maximal run of ids != sep inside the row's length: str.split() on the decoded text; two words are equal iff
+ * they have the same length and the same ids), 3 = both from ONE launch; nl = 2 for levels == 3, else 1.  Outputs, level-major (the
+ * id level first): dist, hyp_n, ref_n [nl][B] int32 = the distance and the two token counts (the lengths at the id level);
+ * totals [nl][3] int64, into which the launch ADDS the batch sums of {dist, hyp_n, ref_n} (the caller zeroes it; integer adds, so
+ * the result does not depend on their order).  The three per-row outputs go together; they or totals may be NULL, not both.
+ * ws: v100_edit_distance_workspace_bytes(B, Th, Tr) bytes (the tokens and word bounds of both levels; -1 = unsupported shape).
+ * B >= 1, 1 <= Th, Tr <= 4096, levels in 1..3, else 1; a NULL required pointer 3; both before anything touches a device. */
+long long v100_edit_distance_workspace_bytes(int B, int Th, int Tr);
+int v100_edit_distance(const long long* hyp, const int* hyp_len, const long long* ref, const int* ref_len, void* ws, int* dist,
+                       int* hyp_n, int* ref_n, long long* totals, int B, int Th, int Tr, int levels, long long sep, void* stream);
 /* TextToAlignTextModel.align (voice100/models/tts.py:89-110) batched: text [B][Lmax] int64, align [B][Lmax][2] float64
  * (gap, length), out [B][Tmax] int64 (zero padded; rows longer than Tmax are cut), out_len [B].  out == NULL: only out_len is
  * written (head + int(sum(align)) + tail per utterance), so the caller can size `out` with one read-back. */

@@ -2,7 +2,8 @@
 greedy CTC decoding (argmax + merge_repeated, voice100/text.py:99-104), ctc_best_path forced alignment
 (voice100/models/align.py:18-66) and the one-launch forced alignment built on it (ctc_align: path, labels, durations and
 score, voice100/align_text.py:39-56), TextToAlignTextModel.align (voice100/models/tts.py:89-110) and the v2
-TextToAlignText.align (voice100/models/_align_v2.py:48-73)."""
+TextToAlignText.align (voice100/models/_align_v2.py:48-73).  edit_distance (K23) has no counterpart in the reference: it scores decoded
+ids against reference ids (character / phone and word error counts) without leaving the device."""
 import torch
 
 from . import _native as N
@@ -104,3 +105,56 @@ def align_expand_v2(text: torch.Tensor, align: torch.Tensor, text_len=None, head
     out = torch.empty((B, tmax), dtype=torch.int64, device=text.device)
     N.call("v100_align_expand_v2", text, al, tl, out, out_len, B, L, tmax, int(head), int(tail))
     return out, out_len
+
+
+def _edit_distance_launch(name, hyp, hyp_len, ref, ref_len, levels, sep, totals, per_row):
+    if not (hyp.is_cuda and ref.is_cuda and hyp_len.is_cuda and ref_len.is_cuda) or (totals is not None and not totals.is_cuda):
+        raise RuntimeError(f"{name}: GPU tensors only")
+    if hyp.dim() != 2 or ref.dim() != 2 or hyp.shape[0] != ref.shape[0] or hyp.shape[0] < 1:
+        raise RuntimeError(f"{name}: hyp [B, Th] and ref [B, Tr] with the same B >= 1, got {list(hyp.shape)} and {list(ref.shape)}")
+    dev = hyp.device
+    B = hyp.shape[0]
+    nl = 2 if levels == 3 else 1
+    if not per_row and totals is None:
+        raise RuntimeError(f"{name}: nothing to compute (per_row=False and no totals)")
+    if totals is not None and (totals.dtype != torch.int64 or totals.numel() != 3 * nl or not totals.is_contiguous()):
+        raise RuntimeError(f"{name}: totals must be a contiguous int64 tensor of {3 * nl} elements")
+    hyp, ref = hyp.to(torch.int64).contiguous(), ref.to(device=dev, dtype=torch.int64).contiguous()
+    hl, rl = hyp_len.to(device=dev, dtype=torch.int32).contiguous(), ref_len.to(device=dev, dtype=torch.int32).contiguous()
+    if hl.numel() != B or rl.numel() != B:
+        raise RuntimeError(f"{name}: hyp_len and ref_len must have {B} elements")
+    if hyp.shape[1] == 0:                                # no column: every row is empty
+        hyp, hl = hyp.new_zeros((B, 1)), torch.zeros_like(hl)
+    if ref.shape[1] == 0:
+        ref, rl = ref.new_zeros((B, 1)), torch.zeros_like(rl)
+    Th, Tr = hyp.shape[1], ref.shape[1]
+    nbytes = N.helper("v100_edit_distance_workspace_bytes", B, Th, Tr)
+    if nbytes <= 0:
+        raise RuntimeError(f"{name}: unsupported shape (Th = {Th} <= 4096 and Tr = {Tr} <= 4096 are the limits)")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    out = tuple(torch.empty((nl, B), dtype=torch.int32, device=dev) for _ in range(3)) if per_row else (None, None, None)
+    N.call("v100_edit_distance", hyp, hl, ref, rl, ws, out[0], out[1], out[2], totals, B, Th, Tr, int(levels), int(sep))
+    return out if per_row else None
+
+
+def edit_distance(hyp: torch.Tensor, hyp_len: torch.Tensor, ref: torch.Tensor, ref_len: torch.Tensor, sep=None, totals=None,
+                  per_row: bool = True):
+    """Batched Levenshtein distance in one launch (K23, csrc/edit_distance.hip): hyp [B, Th] int64 with hyp_len [B], ref [B, Tr] int64
+    with ref_len [B] -> (dist, hyp_n, ref_n), each [B] int32.  Unit costs; lengths are clamped to [0, width] on the device and
+    nothing beyond a row's length is read; ids compare on all 64 bits; Th, Tr <= 4096.
+
+    sep=None: a token is one id (hyp_n / ref_n are the lengths).  sep=<id>: a token is a maximal run of ids != sep inside the row's
+    length -- str.split() on the decoded text -- and two words are equal iff they have the same length and the same ids.
+    totals: an int64 GPU tensor of 3 elements INTO which the launch adds the batch sums of (dist, hyp_n, ref_n); no read-back.
+    per_row=False (with totals): only the totals are computed, and None is returned."""
+    out = _edit_distance_launch("edit_distance", hyp, hyp_len, ref, ref_len, 1 if sep is None else 2, 0 if sep is None else sep,
+                                totals, per_row)
+    return None if out is None else (out[0][0], out[1][0], out[2][0])
+
+
+def edit_distance_both(hyp: torch.Tensor, hyp_len: torch.Tensor, ref: torch.Tensor, ref_len: torch.Tensor, sep: int = 1, totals=None,
+                       per_row: bool = True):
+    """edit_distance at both levels from ONE launch: (dist, hyp_n, ref_n), each [2, B] int32 -- row 0 the id level (characters,
+    the separator counted like any other id), row 1 the word level with separator `sep`.  totals: int64 [2, 3], added into."""
+    out = _edit_distance_launch("edit_distance_both", hyp, hyp_len, ref, ref_len, 3, sep, totals, per_row)
+    return out

@@ -19,7 +19,7 @@ import torch
 import torch.distributed as dist
 
 __all__ = ["shard_indices", "scatter_run", "TTSPipeline", "TTSPipelineV2", "ASRPipeline", "AlignPipeline", "align_records",
-           "GraphedForward"]
+           "ErrorRate", "GraphedForward"]
 
 
 def shard_indices(n_items: int, rank: int, world: int, mode: str = "contiguous") -> torch.Tensor:
@@ -238,6 +238,74 @@ class ASRPipeline:
         ids, n = self(wave, wave_len)
         ids, n = ids.cpu(), n.cpu()
         return [decode(ids[i, :int(n[i])]) for i in range(ids.shape[0])]
+
+
+    @torch.no_grad()
+    def score(self, wav_or_mel: torch.Tensor, lengths, text: torch.Tensor, text_len: torch.Tensor, sep: int = 1):
+        """The ragged call, then decode.edit_distance_both of the decoded ids against text [B, L] int64 / text_len [B] (one launch,
+        no read-back).  Returns {"ids" [B, T'] int64, "ids_len" [B] int32, and per utterance, int32 [B]: "char_errors", "hyp_chars",
+        "chars" (the id level: distance, decoded ids, reference ids), "word_errors", "hyp_words", "words" (words split at `sep`)}."""
+        from .decode import edit_distance_both
+        ids, n = self(wav_or_mel, lengths)
+        dist, hyp_n, ref_n = edit_distance_both(ids, n, text.to(ids.device), text_len.to(ids.device), sep)
+        return {"ids": ids, "ids_len": n, "char_errors": dist[0], "hyp_chars": hyp_n[0], "chars": ref_n[0],
+                "word_errors": dist[1], "hyp_words": hyp_n[1], "words": ref_n[1]}
+
+    @torch.no_grad()
+    def evaluate(self, batches, sep: int = 1):
+        """Error rates over an iterable of (wav_or_mel, lengths, text, text_len): the ragged call and ErrorRate.update per batch, and
+        ONE device-to-host synchronisation at the end.  Returns ErrorRate.compute()."""
+        meter = ErrorRate(sep)
+        for wav_or_mel, lengths, text, text_len in batches:
+            ids, n = self(wav_or_mel, lengths)
+            meter.update(ids, n, text.to(ids.device), text_len.to(ids.device))
+        return meter.compute()
+
+
+class ErrorRate:
+    """Running character (or phone) and word error rates of a validation loop, counted on the device (decode.edit_distance_both, K23).
+
+    update(hyp, hyp_len, ref, ref_len) scores one batch of zero-padded int64 id rows at both levels in one launch and adds the
+    batch sums into an int64 device tensor: no device-to-host synchronisation.  compute() does the one read-back and returns
+    {"cer", "wer", "char_errors", "chars", "word_errors", "words", "utterances"}: the rates are errors / reference tokens, Python
+    floats taken from the integer totals, nan when the reference count is 0.  reset() zeroes the counters.
+
+    sep is the id that separates words; the default 1 is the space of the reference's 29-symbol character vocabulary
+    (voice100/text.py: "_ abc...z'", blank 0, space 1).  sep=None (phone vocabularies: no word level) leaves "wer", "word_errors"
+    and "words" out; "cer" is then the phone error rate."""
+
+    def __init__(self, sep=1):
+        self.sep = sep
+        self.totals = None                               # int64 [levels, 3]: errors, hypothesis tokens, reference tokens
+        self.utterances = 0
+
+    def reset(self):
+        if self.totals is not None:
+            self.totals.zero_()
+        self.utterances = 0
+
+    @torch.no_grad()
+    def update(self, hyp: torch.Tensor, hyp_len: torch.Tensor, ref: torch.Tensor, ref_len: torch.Tensor):
+        from .decode import edit_distance, edit_distance_both
+        if not hyp.is_cuda:
+            raise RuntimeError("ErrorRate.update: GPU tensors only")
+        if self.totals is None:
+            self.totals = torch.zeros((1 if self.sep is None else 2, 3), dtype=torch.int64, device=hyp.device)
+        elif self.totals.device != hyp.device:
+            raise RuntimeError("ErrorRate.update: the counters live on another device")
+        if self.sep is None:
+            edit_distance(hyp, hyp_len, ref, ref_len, None, self.totals, per_row=False)
+        else:
+            edit_distance_both(hyp, hyp_len, ref, ref_len, self.sep, self.totals, per_row=False)
+        self.utterances += hyp.shape[0]
+
+    def compute(self):
+        rows = self.totals.cpu().tolist() if self.totals is not None else [[0, 0, 0]] * (1 if self.sep is None else 2)
+        rate = lambda e, n: e / n if n > 0 else float("nan")  # noqa: E731
+        out = {"cer": rate(rows[0][0], rows[0][2]), "char_errors": rows[0][0], "chars": rows[0][2], "utterances": self.utterances}
+        if self.sep is not None:
+            out.update({"wer": rate(rows[1][0], rows[1][2]), "word_errors": rows[1][0], "words": rows[1][2]})
+        return out
 
 
 class AlignPipeline:
