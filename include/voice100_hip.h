@@ -522,6 +522,20 @@ int v100_ctc_align(const float* logp, const long long* labels, const int* in_len
 long long v100_edit_distance_workspace_bytes(int B, int Th, int Tr);
 int v100_edit_distance(const long long* hyp, const int* hyp_len, const long long* ref, const int* ref_len, void* ws, int* dist,
                        int* hyp_n, int* ref_n, long long* totals, int B, int Th, int Tr, int levels, long long sep, void* stream);
+/* K24, CTC prefix beam search in one launch (csrc/beam.hip): logits [B][T][V] fp32 (the kernel takes the log-softmax itself),
+ * lens [B] int32 or NULL (every row T frames; clamped to [0, T] on the device, nothing beyond a row's length is read).  A beam of W
+ * distinct prefixes, each with the log probability of all its alignments ending in blank / in a label; contributions to the same
+ * prefix merge; the W best totals survive a frame.  Outputs, best first: ids [B][nbest][T] int64 (0 beyond each hypothesis),
+ * ids_len [B][nbest] int32, scores [B][nbest] fp32 = total log probability of the transcript; -inf with length 0 where the beam holds
+ * fewer than nbest hypotheses; a row of length 0 gives the empty hypothesis with score 0.  Ties: the lower candidate index (beam
+ * entry, then class), so two calls give equal bits.
+ * ws: v100_ctc_beam_workspace_bytes(B, T, V, W) bytes (per utterance the prefix trie, 1 + W T nodes, and its child table of
+ * 2 W T slots rounded up to a power of two; -1 = unsupported shape).
+ * B >= 1, 1 <= T <= 4096, 2 <= V <= 128, 1 <= W <= 64, 1 <= nbest <= W, 0 <= blank < V, else 1; a NULL required pointer 3; both
+ * before anything touches a device. */
+long long v100_ctc_beam_workspace_bytes(int B, int T, int V, int W);
+int v100_ctc_beam_search(const float* logits, const int* lens, void* ws, long long* ids, int* ids_len, float* scores, int B, int T, int V,
+                         int W, int nbest, int blank, void* stream);
 /* TextToAlignTextModel.align (voice100/models/tts.py:89-110) batched: text [B][Lmax] int64, align [B][Lmax][2] float64
  * (gap, length), out [B][Tmax] int64 (zero padded; rows longer than Tmax are cut), out_len [B].  out == NULL: only out_len is
  * written (head + int(sum(align)) + tail per utterance), so the caller can size `out` with one read-back. */

@@ -1,0 +1,397 @@
+// K24: CTC prefix beam search, n best transcripts with their total log probabilities, one launch.
+//
+//   beam = at most W distinct label prefixes, each with (pb, pnb) = log probability of all alignments of the frames so far that
+//   collapse to the prefix and end in blank / in a label.  Per frame, lp = log_softmax(x[t]), tot = pb (+) pnb, (+) = logaddexp:
+//     stay    p:      pb' (+)= tot + lp[blank];  pnb' (+)= pnb + lp[e]            (e = last label of p, if any)
+//     extend  p + c:  pnb' (+)= (c == e ? pb : tot) + lp[c]                       (every c != blank)
+//   contributions to the same prefix merge; the W candidates of highest pb' (+) pnb' are the next beam; probability zero is dropped.
+//
+// One workgroup of 256 threads per utterance, no traffic between workgroups.  Per frame:
+//   * identity: a prefix is a node of a trie, node = child(parent node, label), found or created through an open-addressing table
+//     keyed by (parent, label) in the workgroup's own workspace region (64-bit slots {key, node}, one atomicCAS claims a slot or
+//     returns its owner; load <= 1/2).  Node numbers are unique per prefix for the whole utterance, so a prefix that left the beam and
+//     comes back as an extension gets its old node, and "candidate (p, c) is beam entry q" is q.parent == p.node && q.last == c;
+//   * candidates: index k V + c is the extension of beam entry k by c; the slot c == blank holds the stay of k.  Each beam entry q
+//     looks for its parent among the entries (<= W compares): if it is there, the extension (parent, q.last) goes into q's stay and
+//     its own slot becomes -inf.  Scores in LDS, <= 64 x 128 floats;
+//   * selection: radix select (8 bits a pass, one LDS histogram per pass) on the order-preserving integer image of the score finds
+//     the key of rank W.  Every wave scans the histogram for itself (four bins a lane, a DPP scan, a ballot finds the lane that holds
+//     the digit), so a pass costs one barrier; it stops as soon as a bin is taken whole.  Everything above the key is taken, and of
+//     the keys equal to it the lowest candidate indices (an ordered compaction: a contiguous chunk of candidates per lane and a
+//     scan; one wave's work up to 16 candidates a lane, all four waves' beyond).  No float compare decides a tie: two runs give
+//     equal bits;
+//   * new beam (one wave, one lane per entry): node lookup for the extensions, then every score is lowered by the frame's best total,
+//     which goes into an fp64 offset.
+// The log-softmax of frame t + 1 is taken by a second wave beside frame t's stays, from a row loaded a frame before that.  The
+// barriers inside the frame loop wait for LDS only, so that row, the node stores and the table's atomics stay in flight across them.
+// What a frame waits for: 3 barriers, 1 more per radix pass after the first, 2 more where all waves compact (each an LDS round trip
+// plus the phase's own work), the dependent chain of the one wave that takes the stays and builds the beam, and, in a frame that
+// selects an extension, one atomicCAS round trip to L2.  At the end the beam is ranked by total (ties: beam order) and the first
+// nbest prefixes are read back through the parent pointers.
+//
+// Error: the beam's scores stay in (-inf, 0] with the best at 0, so one frame adds a few ulp of numbers of magnitude <= ~30 (the
+// log-softmax, one or two logaddexp, one subtraction; exp and log are the hardware's exp2 / log2 at 1 ulp, the exponent's product
+// carried in two floats): ~1e-6 absolute per frame whatever T is, against a total that falls by ~1 nat or more per frame; the offset
+// is summed in fp64.  Every loop is bounded by T, W, V, 256 or the table size; scores that are NaN or -inf are no candidates, so a
+// row of NaNs empties its beam and runs to the end like any other.
+#include "common.h"
+#include <math.h>
+
+#define BM_THREADS 256
+#define BM_WMAX 64
+#define BM_VMAX 128
+#define BM_TMAX 4096
+#define BM_MINSLOTS 64
+#define BM_SOLO 16                                      // candidates per lane up to which one wave compacts the selection
+
+// LDS-only barrier: the LDS traffic of every wave has landed; global loads, stores and atomics stay in flight
+#define BM_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+
+// Wave-wide scan and maximum on the DPP path: VALU moves, no LDS round trip per step (a __shfl is a ds_bpermute)
+#define BM_DPP(old, v, ctrl, rows, fill) __builtin_amdgcn_update_dpp(old, v, ctrl, rows, 0xf, fill)
+// inclusive prefix sum: lane l gets the sum of lanes 0 .. l
+__device__ __forceinline__ int bm_wave_scan(int v) {
+    v += BM_DPP(0, v, 0x111, 0xf, true);                // row_shr:1, 2, 4, 8: a scan inside each row of 16
+    v += BM_DPP(0, v, 0x112, 0xf, true);
+    v += BM_DPP(0, v, 0x114, 0xf, true);
+    v += BM_DPP(0, v, 0x118, 0xf, true);
+    v += BM_DPP(0, v, 0x142, 0xa, true);                // row_bcast:15 into rows 1 and 3
+    v += BM_DPP(0, v, 0x143, 0xc, true);                // row_bcast:31 into rows 2 and 3
+    return v;
+}
+__device__ __forceinline__ float bm_wave_max(float v) {
+    const int ninf = __builtin_bit_cast(int, -INFINITY);
+#define BM_MAXSTEP(ctrl, rows) v = fmaxf(v, __builtin_bit_cast(float, BM_DPP(ninf, __builtin_bit_cast(int, v), ctrl, rows, false)))
+    BM_MAXSTEP(0x111, 0xf); BM_MAXSTEP(0x112, 0xf); BM_MAXSTEP(0x114, 0xf); BM_MAXSTEP(0x118, 0xf);
+    BM_MAXSTEP(0x142, 0xa); BM_MAXSTEP(0x143, 0xc);
+#undef BM_MAXSTEP
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));      // lane 63 has seen every lane
+}
+__device__ __forceinline__ float bm_wave_total(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wave_sum_dpp_hi(v)), 63));
+}
+
+// exp(d) for d <= 0 and log(u) for u in [1, 128] on the hardware's exp2 / log2 (1 ulp each); the product d log2(e) is carried in two
+// floats so that the error of the exponent does not grow with |d|.  A handful of instructions each: they sit in one wave's
+// dependent chain in every frame.
+__device__ __forceinline__ float bm_exp(float d) {
+    if (d < -87.0f) return 0.0f;
+    const float t = d * 1.44269504089f;
+    float r = fmaf(d, 1.44269504089f, -t);
+    r = fmaf(d, 1.92596299e-8f, r);
+    return __builtin_amdgcn_exp2f(t) * fmaf(r, 0.69314718056f, 1.0f);
+}
+__device__ __forceinline__ float bm_log(float u) { return __builtin_amdgcn_logf(u) * 0.69314718056f; }
+
+__device__ __forceinline__ float bm_lae(float a, float b) {
+    const float m = fmaxf(a, b);
+    if (m == -INFINITY) return -INFINITY;
+    return m + bm_log(1.0f + bm_exp(fminf(a, b) - m));
+}
+
+// order-preserving image of a score; 0 = not a candidate (probability zero, or NaN).  Every finite score maps above 0x007fffff.
+__device__ __forceinline__ unsigned bm_key(float s) {
+    if (!(s > -INFINITY)) return 0u;
+    const unsigned u = __float_as_uint(s);
+    return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
+__global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __restrict__ logits, const int* __restrict__ lens,
+                                                              unsigned char* ws, long long* __restrict__ ids, int* __restrict__ ids_len,
+                                                              float* __restrict__ scores, int T, int V, int W, int nbest, int blank,
+                                                              long long region, int P, unsigned vmagic) {
+    __shared__ float s_score[BM_WMAX * BM_VMAX];        // candidate k V + c: total log probability
+    __shared__ float s_lp[2][BM_VMAX];                  // frame t in s_lp[t & 1]: written one frame ahead
+    __shared__ unsigned s_hist[4][256];                 // one histogram per radix pass
+    __shared__ int s_sel[BM_WMAX];                      // the selected candidates, in index order
+    __shared__ float s_pb[2][BM_WMAX], s_pnb[2][BM_WMAX], s_tot[2][BM_WMAX];     // the beam, double buffered
+    __shared__ int s_node[2][BM_WMAX], s_par[2][BM_WMAX], s_last[2][BM_WMAX], s_len[2][BM_WMAX];
+    __shared__ float s_spb[BM_WMAX], s_spnb[BM_WMAX];   // the stay of each entry
+    __shared__ int s_wsum[BM_THREADS / 64];
+    __shared__ int s_nbeam;                             // entries in the beam
+    __shared__ int s_olen[BM_WMAX], s_onode[BM_WMAX];
+
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int n = lens ? lens[b] : T;
+    n = __builtin_amdgcn_readfirstlane(min(max(n, 0), T));
+    const float* x = logits + (size_t)b * T * V;
+    unsigned long long* table = (unsigned long long*)(ws + (size_t)b * region);          // [P] {key << 32 | node}, 0 = free
+    unsigned* nodes = (unsigned*)(table + P);                                            // [1 + W T] parent << 7 | label
+    const int maxnode = W * T;                                                           // the largest node number
+    int Pb = BM_MINSLOTS;                               // this row's table: 2 W n slots, of the P = 2 W T that the region holds
+    while (Pb < 2 * W * n) Pb <<= 1;
+    const int shift = 32 - __builtin_ctz(Pb);
+
+    {
+        uint4* tz = (uint4*)table;
+        for (int i = tid; i < Pb / 2; i += BM_THREADS) tz[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (tid == 0) {
+        nodes[0] = 0u;
+        s_pb[0][0] = 0.0f; s_pnb[0][0] = -INFINITY; s_tot[0][0] = 0.0f;
+        s_node[0][0] = 0; s_par[0][0] = -1; s_last[0][0] = -1; s_len[0][0] = 0;
+        s_nbeam = 1;
+    }
+    float r0 = -INFINITY, r1 = -INFINITY;               // wave 1: a frame's logits, two per lane
+    auto load_row = [&](int t) {
+        const float* xt = x + (size_t)t * V;
+        if (lane < V) r0 = xt[lane];
+        if (lane + 64 < V) r1 = xt[lane + 64];
+    };
+    auto log_softmax_row = [&](float* dst) {
+        const float m = bm_wave_max(fmaxf(r0, r1));
+        const float e = (lane < V ? bm_exp(r0 - m) : 0.0f) + (lane + 64 < V ? bm_exp(r1 - m) : 0.0f);
+        const float lse = m + bm_log(bm_wave_total(e));
+        if (lane < V) dst[lane] = r0 - lse;
+        if (lane + 64 < V) dst[lane + 64] = r1 - lse;
+    };
+    if (wave == 1 && n > 0) {
+        load_row(0);
+        log_softmax_row(s_lp[0]);
+        if (n > 1) load_row(1);
+    }
+    __threadfence();                                    // the zeroed table is in L2, where the atomics execute
+    __syncthreads();
+
+    double offset = 0.0;                                // wave 0: what the rescaling has taken out of the scores so far
+    int cur = 0;
+    for (int t = 0; t < n; ++t) {
+        const int nb = __builtin_amdgcn_readfirstlane(s_nbeam);
+        const int N = nb * V;
+        const float* lp = s_lp[t & 1];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s_hist[i][tid] = 0u;    // every wave is past the last frame's scans
+        if (wave == 1 && t + 1 < n) {                   // the next frame's log-softmax, beside this frame's stays; its buffer was last
+            log_softmax_row(s_lp[(t + 1) & 1]);         // read in frame t - 1
+            if (t + 2 < n) load_row(t + 2);             // in flight across a whole frame
+        }
+
+        // stays (one thread per entry) and extensions (all threads)
+        float stot = -INFINITY;
+        int kill = -1;
+        if (wave == 0) {
+            const bool live = lane < nb;
+            const int e = live ? s_last[cur][lane] : -1, pq = live ? s_par[cur][lane] : -2, mine = live ? s_node[cur][lane] : -3;
+            int k = -1;                                 // the entry that is this prefix' parent, if it is in the beam
+            for (int i = 0; i < nb; ++i)
+                if (__builtin_amdgcn_readlane(mine, i) == pq) k = i;
+            if (live) {
+                const float spb = s_tot[cur][lane] + lp[blank];
+                float spnb = e >= 0 ? s_pnb[cur][lane] + lp[e] : -INFINITY;
+                if (k >= 0 && e >= 0) {                 // the parent's extension by e is this prefix
+                    const float base = s_last[cur][k] == e ? s_pb[cur][k] : s_tot[cur][k];
+                    spnb = bm_lae(spnb, base + lp[e]);
+                    kill = k * V + e;
+                }
+                s_spb[lane] = spb;
+                s_spnb[lane] = spnb;
+                stot = bm_lae(spb, spnb);
+            }
+        }
+        for (int idx = tid; idx < N; idx += BM_THREADS) {
+            const int k = (int)__umulhi((unsigned)idx, vmagic), c = idx - k * V;
+            const float base = s_last[cur][k] == c ? s_pb[cur][k] : s_tot[cur][k];
+            s_score[idx] = base + lp[c];
+        }
+        BM_BARRIER();
+        if (tid < nb) {
+            s_score[tid * V + blank] = stot;
+            if (kill >= 0) s_score[kill] = -INFINITY;
+        }
+        BM_BARRIER();
+
+        // selection: the key of rank W by radix select, most significant byte first.  Every wave scans the histogram for itself
+        // (four bins a lane, a DPP scan, the lane that holds the digit found by a ballot), so a pass costs one barrier.
+        const int chunk = (N + BM_THREADS - 1) / BM_THREADS;
+        const int lo = min(tid * chunk, N), hi = min(lo + chunk, N);
+        for (int idx = lo; idx < hi; ++idx) {
+            const unsigned key = bm_key(s_score[idx]);
+            if (key) atomicAdd(&s_hist[3][key >> 24], 1u);
+        }
+        BM_BARRIER();
+        unsigned prefix = 0u, mask = 0u;
+        int nvalid = 0, remaining = 0;
+        for (int pass = 3; pass >= 0; --pass) {
+            if (pass < 3) {
+                for (int idx = lo; idx < hi; ++idx) {
+                    const unsigned key = bm_key(s_score[idx]);
+                    if (key && (key & mask) == prefix) atomicAdd(&s_hist[pass][(key >> (8 * pass)) & 255u], 1u);
+                }
+                BM_BARRIER();
+            }
+            int h[4], sum = 0;                          // lane l holds digits 255 - 4 l - j: the scan over the lanes counts from the top
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { h[j] = (int)s_hist[pass][255 - 4 * lane - j]; sum += h[j]; }
+            const int S = bm_wave_scan(sum);
+            if (pass == 3) {
+                nvalid = __builtin_amdgcn_readlane(S, 63);               // every candidate of probability > 0
+                remaining = min(W, nvalid);
+                if (nvalid <= W) break;                 // fewer candidates than places: all of them (mask 0: every key "equals" the prefix)
+            }
+            int acc = S - sum, digit = 0, rem = 0, exact = 0;
+            const bool hit = S >= remaining && acc < remaining;          // exactly one lane
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (hit && acc < remaining && acc + h[j] >= remaining) {
+                    digit = 255 - 4 * lane - j;
+                    rem = remaining - acc;
+                    exact = h[j] == rem;
+                }
+                acc += h[j];
+            }
+            const unsigned long long who = __ballot(hit);
+            const int src = who ? __builtin_ctzll(who) : 0;
+            prefix |= (unsigned)__builtin_amdgcn_readlane(digit, src) << (8 * pass);
+            mask |= 0xffu << (8 * pass);
+            remaining = __builtin_amdgcn_readlane(rem, src);
+            if (__builtin_amdgcn_readlane(exact, src)) break;            // every key under this prefix is taken: the lower bytes decide nothing
+        }
+
+        // ordered compaction: above the prefix, then the first `remaining` of those equal to it.  Up to 16 candidates a lane it is
+        // wave 0's alone (its own LDS traffic is in order: no barrier before it reads the list back); beyond, all four waves' with
+        // one exchange of the waves' counts.
+        auto compact = [&](int c0, int c1, int base) {
+            int gb = base & 0xffff, eb = base >> 16;
+            for (int idx = c0; idx < c1; ++idx) {
+                const unsigned key = bm_key(s_score[idx]);
+                if (!key) continue;
+                int pos = -1;
+                if ((key & mask) > prefix) { pos = gb + min(eb, remaining); ++gb; }
+                else if ((key & mask) == prefix) { if (eb < remaining) pos = gb + eb; ++eb; }
+                if (pos >= 0 && pos < BM_WMAX) s_sel[pos] = idx;
+            }
+        };
+        auto count = [&](int c0, int c1) {
+            int g = 0, e = 0;
+            for (int idx = c0; idx < c1; ++idx) {
+                const unsigned key = bm_key(s_score[idx]);
+                if (key) {
+                    g += (key & mask) > prefix;
+                    e += (key & mask) == prefix;
+                }
+            }
+            return g | (e << 16);                       // both counts <= 8192
+        };
+        if (N <= 64 * BM_SOLO) {
+            if (wave == 0) {
+                const int ch = (N + 63) / 64, c0 = min(lane * ch, N), c1 = min(c0 + ch, N);
+                const int packed = count(c0, c1);
+                compact(c0, c1, bm_wave_scan(packed) - packed);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            }
+        } else {
+            const int packed = count(lo, hi);
+            const int incl = bm_wave_scan(packed);
+            if (lane == 63) s_wsum[wave] = incl;
+            BM_BARRIER();
+            int excl = incl - packed;
+            for (int w = 0; w < wave; ++w) excl += s_wsum[w];
+            compact(lo, hi, excl);
+            BM_BARRIER();
+        }
+
+        // the next beam (wave 0)
+        const int nsel = min(W, nvalid);
+        const int nx = cur ^ 1;
+        if (wave == 0) {
+            float pb = -INFINITY, pnb = -INFINITY, tot = -INFINITY;
+            int node = 0, par = -1, last = -1, len = 0;
+            if (lane < nsel) {
+                const int idx = s_sel[lane];
+                const int k = (int)__umulhi((unsigned)idx, vmagic), c = idx - k * V;
+                tot = s_score[idx];
+                if (c == blank) {
+                    pb = s_spb[k]; pnb = s_spnb[k];
+                    node = s_node[cur][k]; par = s_par[cur][k]; last = s_last[cur][k]; len = s_len[cur][k];
+                } else {
+                    pnb = tot;
+                    last = c; len = s_len[cur][k] + 1; par = s_node[cur][k];
+                    const unsigned fresh = 1u + (unsigned)t * (unsigned)W + (unsigned)lane;      // <= W T
+                    const unsigned key = (unsigned)par * 128u + (unsigned)c + 1u;                // < 2^27
+                    const unsigned long long mine = ((unsigned long long)key << 32) | fresh;
+                    unsigned slot = (key * 0x9E3779B1u) >> shift;
+                    node = (int)fresh;
+                    for (int probe = 0; probe < Pb; ++probe) {
+                        const unsigned long long old = atomicCAS(&table[slot], 0ull, mine);
+                        if (old == 0ull) { nodes[fresh] = ((unsigned)par << 7) | (unsigned)c; break; }       // a new prefix
+                        if ((unsigned)(old >> 32) == key) { node = (int)(unsigned)(old & 0xffffffffull); break; }
+                        slot = (slot + 1u) & (unsigned)(Pb - 1);                                 // another prefix' slot
+                    }
+                }
+            }
+            const float best = bm_wave_max(tot);
+            if (lane < nsel) {
+                s_pb[nx][lane] = pb - best; s_pnb[nx][lane] = pnb - best; s_tot[nx][lane] = tot - best;
+                s_node[nx][lane] = node; s_par[nx][lane] = par; s_last[nx][lane] = last; s_len[nx][lane] = len;
+            }
+            if (nsel > 0) offset += (double)best;
+            if (lane == 0) s_nbeam = nsel;
+        }
+        cur = nx;
+        BM_BARRIER();
+    }
+
+    // rank the beam by total (ties: beam order), report the first nbest
+    const int nb = s_nbeam;
+    if (wave == 0) {
+        const float tot = lane < nb ? s_tot[cur][lane] : -INFINITY;
+        int rank = 0;
+        for (int i = 0; i < nb; ++i) {
+            const float ti = s_tot[cur][i];
+            rank += (ti > tot) || (ti == tot && i < lane);
+        }
+        if (lane < nb) s_sel[rank] = lane;
+    }
+    __syncthreads();
+    if (wave == 0 && lane < nbest) {
+        int len = 0, node = 0;
+        float sc = -INFINITY;
+        if (lane < nb) {
+            const int j = min(max(s_sel[lane], 0), BM_WMAX - 1);
+            len = min(max(s_len[cur][j], 0), n);
+            node = s_node[cur][j];
+            sc = (float)((double)s_tot[cur][j] + offset);
+        }
+        scores[(size_t)b * nbest + lane] = sc;
+        ids_len[(size_t)b * nbest + lane] = len;
+        s_olen[lane] = len;
+        s_onode[lane] = node;
+    }
+    __syncthreads();
+    long long* out = ids + (size_t)b * nbest * T;
+    for (int r = 0; r < nbest; ++r)
+        for (int i = s_olen[r] + tid; i < T; i += BM_THREADS) out[(size_t)r * T + i] = 0;
+    if (tid < nbest) {                                  // the labels, last to first, through the parent pointers
+        int p = s_onode[tid];
+        for (int i = s_olen[tid] - 1; i >= 0; --i) {
+            const unsigned v = nodes[min(max(p, 0), maxnode)];
+            out[(size_t)tid * T + i] = (long long)(v & 127u);
+            p = (int)(v >> 7);
+        }
+    }
+}
+
+static inline bool bm_shape_ok(int B, int T, int V, int W) {
+    return B >= 1 && T >= 1 && T <= BM_TMAX && V >= 2 && V <= BM_VMAX && W >= 1 && W <= BM_WMAX;
+}
+static inline int bm_slots(int T, int W) {
+    int P = BM_MINSLOTS;
+    while (P < 2 * W * T) P <<= 1;                       // <= 2^19
+    return P;
+}
+static inline long long bm_region(int T, int W) { return 8ll * bm_slots(T, W) + 4ll * ((1 + W * T + 3) & ~3); }
+
+extern "C" long long v100_ctc_beam_workspace_bytes(int B, int T, int V, int W) {
+    if (!bm_shape_ok(B, T, V, W)) return -1;
+    return (long long)B * bm_region(T, W);
+}
+
+extern "C" int v100_ctc_beam_search(const float* logits, const int* lens, void* ws, long long* ids, int* ids_len, float* scores, int B,
+                                    int T, int V, int W, int nbest, int blank, void* stream) {
+    if (!logits || !ws || !ids || !ids_len || !scores) return V100_ERR_NULL;
+    if (!bm_shape_ok(B, T, V, W) || nbest < 1 || nbest > W || blank < 0 || blank >= V) return V100_ERR_SHAPE;
+    const unsigned vmagic = (unsigned)((1ull << 32) / (unsigned)V) + 1u;     // idx / V == umulhi(idx, vmagic) for idx < 2^13, V <= 128
+    V100_GGL(ctc_beam_kernel, dim3(B), dim3(BM_THREADS), 0, (hipStream_t)stream, logits, lens, (unsigned char*)ws, ids, ids_len, scores, T,
+             V, W, nbest, blank, bm_region(T, W), bm_slots(T, W), vmagic);
+    return v100_launch_status();
+}

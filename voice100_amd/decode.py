@@ -3,7 +3,8 @@ greedy CTC decoding (argmax + merge_repeated, voice100/text.py:99-104), ctc_best
 (voice100/models/align.py:18-66) and the one-launch forced alignment built on it (ctc_align: path, labels, durations and
 score, voice100/align_text.py:39-56), TextToAlignTextModel.align (voice100/models/tts.py:89-110) and the v2
 TextToAlignText.align (voice100/models/_align_v2.py:48-73).  edit_distance (K23) has no counterpart in the reference: it scores decoded
-ids against reference ids (character / phone and word error counts) without leaving the device."""
+ids against reference ids (character / phone and word error counts) without leaving the device.  Neither has ctc_beam_search (K24):
+the CTC prefix beam search, n best transcripts with their total log probabilities, where the reference decodes greedily."""
 import torch
 
 from . import _native as N
@@ -158,3 +159,33 @@ def edit_distance_both(hyp: torch.Tensor, hyp_len: torch.Tensor, ref: torch.Tens
     the separator counted like any other id), row 1 the word level with separator `sep`.  totals: int64 [2, 3], added into."""
     out = _edit_distance_launch("edit_distance_both", hyp, hyp_len, ref, ref_len, 3, sep, totals, per_row)
     return out
+
+
+def ctc_beam_search(logits: torch.Tensor, lengths: torch.Tensor = None, beam_size: int = 16, nbest: int = 1, blank: int = 0):
+    """CTC prefix beam search in one launch (K24, csrc/beam.hip): logits [B, T, V] fp32 (the model's output, as ctc_greedy_decode takes
+    it; the kernel normalises) -> (ids [B, nbest, T] int64 zero-padded, lens [B, nbest] int32, scores [B, nbest] fp32), best first.
+
+    A score is the total log probability of the transcript (the sum over all its alignments, not the best one).  Where the beam holds
+    fewer than nbest hypotheses the score is -inf and the length 0; a row of length 0 gives the empty hypothesis with score 0.
+    lengths are clamped to [0, T] on the device and nothing beyond a row's length is read.  Ties break on the candidate index, so two
+    calls give equal bits.  Limits: 1 <= beam_size <= 64, 2 <= V <= 128, 1 <= nbest <= beam_size, 0 <= blank < V, 1 <= T <= 4096."""
+    if not logits.is_cuda or (lengths is not None and not lengths.is_cuda):
+        raise RuntimeError("ctc_beam_search: GPU tensors only")
+    if logits.dim() != 3:
+        raise RuntimeError(f"ctc_beam_search: logits must be [B, T, V], got {list(logits.shape)}")
+    logits = logits.contiguous().float()
+    B, T, V = logits.shape
+    W, nbest, blank = int(beam_size), int(nbest), int(blank)
+    nbytes = N.helper("v100_ctc_beam_workspace_bytes", B, T, V, W) if B >= 1 else -1
+    if nbytes <= 0 or not 1 <= nbest <= W or not 0 <= blank < V:
+        raise RuntimeError(f"ctc_beam_search: unsupported shape or argument (B = {B} >= 1, 1 <= T = {T} <= 4096, 2 <= V = {V} <= 128, "
+                           f"1 <= beam_size = {W} <= 64, 1 <= nbest = {nbest} <= beam_size and 0 <= blank = {blank} < V are the limits)")
+    lens = lengths.to(device=logits.device, dtype=torch.int32).contiguous() if lengths is not None else None
+    if lens is not None and lens.numel() != B:
+        raise RuntimeError(f"ctc_beam_search: lengths must have {B} elements")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=logits.device)
+    ids = torch.empty((B, nbest, T), dtype=torch.int64, device=logits.device)
+    ids_len = torch.empty((B, nbest), dtype=torch.int32, device=logits.device)
+    scores = torch.empty((B, nbest), dtype=torch.float32, device=logits.device)
+    N.call("v100_ctc_beam_search", logits, lens, ws, ids, ids_len, scores, B, T, V, W, nbest, blank)
+    return ids, ids_len, scores
