@@ -536,6 +536,21 @@ int v100_edit_distance(const long long* hyp, const int* hyp_len, const long long
 long long v100_ctc_beam_workspace_bytes(int B, int T, int V, int W);
 int v100_ctc_beam_search(const float* logits, const int* lens, void* ws, long long* ids, int* ids_len, float* scores, int B, int T, int V,
                          int W, int nbest, int blank, void* stream);
+/* K25, the same search with an n-gram language model fused into the per-frame selection (shallow fusion): the beam is ranked by
+ * key = log p_ctc + alpha log p_lm + beta length.  The LM is a deterministic automaton over the logits' own label ids, back-off
+ * already resolved: lm_logp [S][V] fp32 natural log, lm_next [S][V] int32 (the state after (state, label); clamped to [0, S) on the
+ * device), lm_final [S] fp32 = log p(end of sentence | state), added (times alpha) before the final ranking iff use_eos.  The blank
+ * column of both tables never enters a result.  An extension of an entry by c adds lm_logp[state][c] to its LM sum and 1 to its length; a
+ * stay keeps both; the CTC recurrences never see the LM, and a candidate whose CTC total is -inf or NaN stays no candidate.
+ * Outputs as K24's, with scores = the key, ctc_scores [B][nbest] = K24's score of the same transcript, lm_scores [B][nbest] = the
+ * LM sum (lm_final included iff use_eos); -inf, -inf, 0 where there is no hypothesis.  alpha = beta = 0, use_eos = 0 gives K24's
+ * ids, lengths and (in ctc_scores) scores bit for bit.  ws: v100_ctc_beam_workspace_bytes, as K24.
+ * K24's limits, and 1 <= S, S V <= 2^28, 0 <= start_state < S, alpha and beta finite, else 1; a NULL pointer (lens excepted) 3;
+ * both before anything touches a device. */
+int v100_ctc_beam_search_lm(const float* logits, const int* lens, void* ws, long long* ids, int* ids_len, float* scores,
+                            const float* lm_logp, const int* lm_next, const float* lm_final, int S, int start_state, float alpha,
+                            float beta, int use_eos, float* ctc_scores, float* lm_scores, int B, int T, int V, int W, int nbest,
+                            int blank, void* stream);
 /* TextToAlignTextModel.align (voice100/models/tts.py:89-110) batched: text [B][Lmax] int64, align [B][Lmax][2] float64
  * (gap, length), out [B][Tmax] int64 (zero padded; rows longer than Tmax are cut), out_len [B].  out == NULL: only out_len is
  * written (head + int(sum(align)) + tail per utterance), so the caller can size `out` with one read-back. */

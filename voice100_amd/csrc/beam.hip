@@ -34,6 +34,15 @@
 // carried in two floats): ~1e-6 absolute per frame whatever T is, against a total that falls by ~1 nat or more per frame; the offset
 // is summed in fp64.  Every loop is bounded by T, W, V, 256 or the table size; scores that are NaN or -inf are no candidates, so a
 // row of NaNs empties its beam and runs to the end like any other.
+//
+// K25: the fused form, ctc_beam_kernel<true>, ranks by key = tot + alpha lm + beta len with an n-gram language model given as a
+// deterministic automaton (logp [S][V], next [S][V], final [S]).  An entry also carries its state and its LM sum; an extension by c
+// adds logp[state][c] and 1 to the length and moves to next[state][c], a stay keeps all three; lm is a function of the prefix, so a
+// returning prefix gets the same value from its parent and nothing is stored per node.  The candidate array holds the key (selection
+// and compaction are unchanged); the wave that builds the beam takes the CTC total of a selected stay from s_stot and recomputes an
+// extension's as the same sum.  The LM part is rescaled like the scores: lm is kept less that of the entry with the highest key,
+// the amount goes into an fp64 offset, and the length enters as a difference from that entry's.  The CTC recurrences never see the
+// LM.  ctc_beam_kernel<false> is K24, instruction for instruction.
 #include "common.h"
 #include <math.h>
 
@@ -96,10 +105,22 @@ __device__ __forceinline__ unsigned bm_key(float s) {
     return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
 }
 
+// K25: what the fused form (LM = true) takes beside K24's arguments; the plain form never reads it
+struct BmLm {
+    const float* logp;                                  // [S][V] natural log, back-off resolved
+    const int* next;                                    // [S][V] the state after (state, label)
+    const float* fin;                                   // [S] log p(</s> | state)
+    float* ctc_scores;                                  // [B][nbest]
+    float* lm_scores;                                   // [B][nbest]
+    int S, start, use_eos;
+    float alpha, beta;
+};
+
+template <bool LM>
 __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __restrict__ logits, const int* __restrict__ lens,
                                                               unsigned char* ws, long long* __restrict__ ids, int* __restrict__ ids_len,
                                                               float* __restrict__ scores, int T, int V, int W, int nbest, int blank,
-                                                              long long region, int P, unsigned vmagic) {
+                                                              long long region, int P, unsigned vmagic, BmLm lm) {
     __shared__ float s_score[BM_WMAX * BM_VMAX];        // candidate k V + c: total log probability
     __shared__ float s_lp[2][BM_VMAX];                  // frame t in s_lp[t & 1]: written one frame ahead
     __shared__ unsigned s_hist[4][256];                 // one histogram per radix pass
@@ -110,6 +131,10 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
     __shared__ int s_wsum[BM_THREADS / 64];
     __shared__ int s_nbeam;                             // entries in the beam
     __shared__ int s_olen[BM_WMAX], s_onode[BM_WMAX];
+    // K25 (LM only; the plain form does not touch them and they take no LDS there): per entry the automaton state, the LM log
+    // probability less lmoff, the rank key's LM part bias = alpha lm + beta (len - the reference entry's), and the stay's CTC total
+    __shared__ int s_state[2][BM_WMAX];
+    __shared__ float s_lm[2][BM_WMAX], s_bias[2][BM_WMAX], s_stot[BM_WMAX];
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int n = lens ? lens[b] : T;
@@ -131,6 +156,7 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
         s_pb[0][0] = 0.0f; s_pnb[0][0] = -INFINITY; s_tot[0][0] = 0.0f;
         s_node[0][0] = 0; s_par[0][0] = -1; s_last[0][0] = -1; s_len[0][0] = 0;
         s_nbeam = 1;
+        if constexpr (LM) { s_state[0][0] = lm.start; s_lm[0][0] = 0.0f; s_bias[0][0] = 0.0f; }
     }
     float r0 = -INFINITY, r1 = -INFINITY;               // wave 1: a frame's logits, two per lane
     auto load_row = [&](int t) {
@@ -154,6 +180,7 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
     __syncthreads();
 
     double offset = 0.0;                                // wave 0: what the rescaling has taken out of the scores so far
+    double lmoff = 0.0;                                 // K25, wave 0: what it has taken out of the LM log probabilities
     int cur = 0;
     for (int t = 0; t < n; ++t) {
         const int nb = __builtin_amdgcn_readfirstlane(s_nbeam);
@@ -186,16 +213,24 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
                 s_spb[lane] = spb;
                 s_spnb[lane] = spnb;
                 stot = bm_lae(spb, spnb);
+                if constexpr (LM) s_stot[lane] = stot;
             }
         }
         for (int idx = tid; idx < N; idx += BM_THREADS) {
             const int k = (int)__umulhi((unsigned)idx, vmagic), c = idx - k * V;
             const float base = s_last[cur][k] == c ? s_pb[cur][k] : s_tot[cur][k];
-            s_score[idx] = base + lp[c];
+            if constexpr (LM) {                         // the rank key; a CTC total of -inf or NaN stays "no candidate"
+                const float ctc = base + lp[c];
+                const float l = lm.logp[(size_t)s_state[cur][k] * V + c];       // the states are inside [0, S): clamped where they are set
+                s_score[idx] = ctc > -INFINITY ? ctc + (s_bias[cur][k] + (lm.alpha * l + lm.beta)) : -INFINITY;
+            } else {
+                s_score[idx] = base + lp[c];
+            }
         }
         BM_BARRIER();
         if (tid < nb) {
-            s_score[tid * V + blank] = stot;
+            if constexpr (LM) s_score[tid * V + blank] = stot > -INFINITY ? stot + s_bias[cur][tid] : -INFINITY;
+            else s_score[tid * V + blank] = stot;
             if (kill >= 0) s_score[kill] = -INFINITY;
         }
         BM_BARRIER();
@@ -296,10 +331,27 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
         if (wave == 0) {
             float pb = -INFINITY, pnb = -INFINITY, tot = -INFINITY;
             int node = 0, par = -1, last = -1, len = 0;
+            float key = -INFINITY, lmv = 0.0f;          // K25: the rank key, the LM log probability and the state of the new entry
+            int state = 0;
             if (lane < nsel) {
                 const int idx = s_sel[lane];
                 const int k = (int)__umulhi((unsigned)idx, vmagic), c = idx - k * V;
                 tot = s_score[idx];
+                if constexpr (LM) {                     // s_score holds the key: the CTC total is the stay's, or the same sum again
+                    key = tot;
+                    state = s_state[cur][k];
+                    lmv = s_lm[cur][k];
+                    if (c == blank) {
+                        tot = s_stot[k];
+                    } else {
+                        const size_t at = (size_t)state * V + c;    // both loads are under way while the table is asked
+                        const float l = lm.logp[at];
+                        const int to = lm.next[at];
+                        tot = (s_last[cur][k] == c ? s_pb[cur][k] : s_tot[cur][k]) + lp[c];
+                        lmv += l;
+                        state = min(max(to, 0), lm.S - 1);
+                    }
+                }
                 if (c == blank) {
                     pb = s_spb[k]; pnb = s_spnb[k];
                     node = s_node[cur][k]; par = s_par[cur][k]; last = s_last[cur][k]; len = s_len[cur][k];
@@ -324,6 +376,19 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
                 s_pb[nx][lane] = pb - best; s_pnb[nx][lane] = pnb - best; s_tot[nx][lane] = tot - best;
                 s_node[nx][lane] = node; s_par[nx][lane] = par; s_last[nx][lane] = last; s_len[nx][lane] = len;
             }
+            if constexpr (LM) {                         // the LM part is kept relative to the entry of the highest key (ties: the first)
+                const float top = bm_wave_max(key);
+                const unsigned long long who = __ballot(lane < nsel && key == top);
+                const int src = who ? __builtin_ctzll(who) : 0;
+                const float lmref = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lmv), src));
+                const int lenref = __builtin_amdgcn_readlane(len, src);
+                if (lane < nsel) {
+                    const float rel = lmv - lmref;
+                    s_state[nx][lane] = state; s_lm[nx][lane] = rel;
+                    s_bias[nx][lane] = lm.alpha * rel + lm.beta * (float)(len - lenref);
+                }
+                if (nsel > 0) lmoff += (double)lmref;
+            }
             if (nsel > 0) offset += (double)best;
             if (lane == 0) s_nbeam = nsel;
         }
@@ -334,10 +399,20 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
     // rank the beam by total (ties: beam order), report the first nbest
     const int nb = s_nbeam;
     if (wave == 0) {
-        const float tot = lane < nb ? s_tot[cur][lane] : -INFINITY;
+        float tot = lane < nb ? s_tot[cur][lane] : -INFINITY;
+        if constexpr (LM) {                             // rank by the key, with alpha log p(</s> | state) where the caller wants it
+            if (lane < nb) {
+                const float fin = lm.use_eos ? lm.fin[min(max(s_state[cur][lane], 0), lm.S - 1)] : 0.0f;
+                const float all = s_lm[cur][lane] + fin;
+                s_lm[cur][lane] = all;
+                tot = tot > -INFINITY ? tot + (s_bias[cur][lane] + lm.alpha * fin) : -INFINITY;
+                if (!(tot == tot)) tot = -INFINITY;
+            }
+            s_spb[lane] = tot;
+        }
         int rank = 0;
         for (int i = 0; i < nb; ++i) {
-            const float ti = s_tot[cur][i];
+            const float ti = LM ? s_spb[i] : s_tot[cur][i];
             rank += (ti > tot) || (ti == tot && i < lane);
         }
         if (lane < nb) s_sel[rank] = lane;
@@ -346,11 +421,19 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
     if (wave == 0 && lane < nbest) {
         int len = 0, node = 0;
         float sc = -INFINITY;
+        double lmsum = 0.0, ctc64 = 0.0;
         if (lane < nb) {
             const int j = min(max(s_sel[lane], 0), BM_WMAX - 1);
             len = min(max(s_len[cur][j], 0), n);
             node = s_node[cur][j];
-            sc = (float)((double)s_tot[cur][j] + offset);
+            ctc64 = (double)s_tot[cur][j] + offset;
+            sc = (float)ctc64;
+            if constexpr (LM) lmsum = (double)s_lm[cur][j] + lmoff;
+        }
+        if constexpr (LM) {                             // the key in fp64 from its three parts; -inf, -inf, 0 where there is no hypothesis
+            lm.ctc_scores[(size_t)b * nbest + lane] = sc;
+            lm.lm_scores[(size_t)b * nbest + lane] = (float)lmsum;
+            if (lane < nb) sc = (float)(ctc64 + (double)lm.alpha * lmsum + (double)lm.beta * (double)len);
         }
         scores[(size_t)b * nbest + lane] = sc;
         ids_len[(size_t)b * nbest + lane] = len;
@@ -391,7 +474,25 @@ extern "C" int v100_ctc_beam_search(const float* logits, const int* lens, void* 
     if (!logits || !ws || !ids || !ids_len || !scores) return V100_ERR_NULL;
     if (!bm_shape_ok(B, T, V, W) || nbest < 1 || nbest > W || blank < 0 || blank >= V) return V100_ERR_SHAPE;
     const unsigned vmagic = (unsigned)((1ull << 32) / (unsigned)V) + 1u;     // idx / V == umulhi(idx, vmagic) for idx < 2^13, V <= 128
-    V100_GGL(ctc_beam_kernel, dim3(B), dim3(BM_THREADS), 0, (hipStream_t)stream, logits, lens, (unsigned char*)ws, ids, ids_len, scores, T,
-             V, W, nbest, blank, bm_region(T, W), bm_slots(T, W), vmagic);
+    V100_GGL(ctc_beam_kernel<false>, dim3(B), dim3(BM_THREADS), 0, (hipStream_t)stream, logits, lens, (unsigned char*)ws, ids, ids_len,
+             scores, T, V, W, nbest, blank, bm_region(T, W), bm_slots(T, W), vmagic, BmLm{});
+    return v100_launch_status();
+}
+
+// K25: the same search ranked by log p_ctc + alpha log p_lm + beta length (see the header); the workspace is K24's
+extern "C" int v100_ctc_beam_search_lm(const float* logits, const int* lens, void* ws, long long* ids, int* ids_len, float* scores,
+                                       const float* lm_logp, const int* lm_next, const float* lm_final, int S, int start_state,
+                                       float alpha, float beta, int use_eos, float* ctc_scores, float* lm_scores, int B, int T, int V,
+                                       int W, int nbest, int blank, void* stream) {
+    if (!logits || !ws || !ids || !ids_len || !scores || !lm_logp || !lm_next || !lm_final || !ctc_scores || !lm_scores)
+        return V100_ERR_NULL;
+    if (!bm_shape_ok(B, T, V, W) || nbest < 1 || nbest > W || blank < 0 || blank >= V) return V100_ERR_SHAPE;
+    if (S < 1 || (long long)S * V > (1ll << 28) || start_state < 0 || start_state >= S || !(alpha == alpha) || !(beta == beta) ||
+        fabsf(alpha) == INFINITY || fabsf(beta) == INFINITY)
+        return V100_ERR_SHAPE;
+    const unsigned vmagic = (unsigned)((1ull << 32) / (unsigned)V) + 1u;
+    const BmLm lm{lm_logp, lm_next, lm_final, ctc_scores, lm_scores, S, start_state, use_eos != 0, alpha, beta};
+    V100_GGL(ctc_beam_kernel<true>, dim3(B), dim3(BM_THREADS), 0, (hipStream_t)stream, logits, lens, (unsigned char*)ws, ids, ids_len,
+             scores, T, V, W, nbest, blank, bm_region(T, W), bm_slots(T, W), vmagic, lm);
     return v100_launch_status();
 }

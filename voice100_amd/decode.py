@@ -4,7 +4,10 @@ greedy CTC decoding (argmax + merge_repeated, voice100/text.py:99-104), ctc_best
 score, voice100/align_text.py:39-56), TextToAlignTextModel.align (voice100/models/tts.py:89-110) and the v2
 TextToAlignText.align (voice100/models/_align_v2.py:48-73).  edit_distance (K23) has no counterpart in the reference: it scores decoded
 ids against reference ids (character / phone and word error counts) without leaving the device.  Neither has ctc_beam_search (K24):
-the CTC prefix beam search, n best transcripts with their total log probabilities, where the reference decodes greedily."""
+the CTC prefix beam search, n best transcripts with their total log probabilities, where the reference decodes greedily, nor its
+fused form (K25): the same search with an lm.NGramLM voting inside every frame's selection."""
+import math
+
 import torch
 
 from . import _native as N
@@ -161,14 +164,20 @@ def edit_distance_both(hyp: torch.Tensor, hyp_len: torch.Tensor, ref: torch.Tens
     return out
 
 
-def ctc_beam_search(logits: torch.Tensor, lengths: torch.Tensor = None, beam_size: int = 16, nbest: int = 1, blank: int = 0):
+def ctc_beam_search(logits: torch.Tensor, lengths: torch.Tensor = None, beam_size: int = 16, nbest: int = 1, blank: int = 0, lm=None,
+                    lm_weight: float = 0.5, length_bonus: float = 0.0, use_eos: bool = True):
     """CTC prefix beam search in one launch (K24, csrc/beam.hip): logits [B, T, V] fp32 (the model's output, as ctc_greedy_decode takes
     it; the kernel normalises) -> (ids [B, nbest, T] int64 zero-padded, lens [B, nbest] int32, scores [B, nbest] fp32), best first.
 
     A score is the total log probability of the transcript (the sum over all its alignments, not the best one).  Where the beam holds
     fewer than nbest hypotheses the score is -inf and the length 0; a row of length 0 gives the empty hypothesis with score 0.
     lengths are clamped to [0, T] on the device and nothing beyond a row's length is read.  Ties break on the candidate index, so two
-    calls give equal bits.  Limits: 1 <= beam_size <= 64, 2 <= V <= 128, 1 <= nbest <= beam_size, 0 <= blank < V, 1 <= T <= 4096."""
+    calls give equal bits.  Limits: 1 <= beam_size <= 64, 2 <= V <= 128, 1 <= nbest <= beam_size, 0 <= blank < V, 1 <= T <= 4096.
+
+    lm: a compiled lm.NGramLM on the logits' device (K25, shallow fusion inside the launch).  The beam is then ranked, in every frame,
+    by score = log p_ctc + lm_weight * log p_lm + length_bonus * length, with use_eos the LM's end-of-sentence probability enters
+    before the final ranking, and the call returns (ids, lens, scores, ctc_scores, lm_scores): ctc_scores is what the call without an
+    LM reports for the same transcript, lm_scores the LM's log probability of it; -inf, -inf, 0 where there is no hypothesis."""
     if not logits.is_cuda or (lengths is not None and not lengths.is_cuda):
         raise RuntimeError("ctc_beam_search: GPU tensors only")
     if logits.dim() != 3:
@@ -183,9 +192,32 @@ def ctc_beam_search(logits: torch.Tensor, lengths: torch.Tensor = None, beam_siz
     lens = lengths.to(device=logits.device, dtype=torch.int32).contiguous() if lengths is not None else None
     if lens is not None and lens.numel() != B:
         raise RuntimeError(f"ctc_beam_search: lengths must have {B} elements")
+    if lm is not None:
+        tables = (getattr(lm, "logp", None), getattr(lm, "next", None), getattr(lm, "final", None))
+        if any(t is None for t in tables):
+            raise RuntimeError("ctc_beam_search: the language model is not compiled (NGramLM.compile().to(device) first)")
+        logp, nxt, fin = tables
+        if logp.dim() != 2 or logp.shape[0] < 1 or nxt.shape != logp.shape or fin.shape != logp.shape[:1]:
+            raise RuntimeError(f"ctc_beam_search: the language model is empty or malformed (logp {list(logp.shape)}, next "
+                               f"{list(nxt.shape)}, final {list(fin.shape)}; [S, V], [S, V], [S] with S >= 1 expected)")
+        if any(t.device != logits.device for t in tables):
+            raise RuntimeError(f"ctc_beam_search: the language model is on {logp.device}, the logits on {logits.device} (lm.to(device))")
+        S = logp.shape[0]
+        if logp.shape[1] != V or S * V > 1 << 28 or not 0 <= int(lm.start) < S or blank != int(lm.blank):
+            raise RuntimeError(f"ctc_beam_search: the language model has V = {logp.shape[1]}, blank = {lm.blank}, S = {S} and start state "
+                               f"{lm.start}; V = {V}, blank = {blank}, S V <= 2^28 and 0 <= start < S are required")
+        alpha, beta = float(lm_weight), float(length_bonus)
+        if not (math.isfinite(alpha) and math.isfinite(beta)):
+            raise RuntimeError(f"ctc_beam_search: lm_weight = {alpha} and length_bonus = {beta} must be finite")
+        logp, nxt, fin = logp.contiguous().float(), nxt.contiguous().to(torch.int32), fin.contiguous().float()
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=logits.device)
     ids = torch.empty((B, nbest, T), dtype=torch.int64, device=logits.device)
     ids_len = torch.empty((B, nbest), dtype=torch.int32, device=logits.device)
     scores = torch.empty((B, nbest), dtype=torch.float32, device=logits.device)
-    N.call("v100_ctc_beam_search", logits, lens, ws, ids, ids_len, scores, B, T, V, W, nbest, blank)
-    return ids, ids_len, scores
+    if lm is None:
+        N.call("v100_ctc_beam_search", logits, lens, ws, ids, ids_len, scores, B, T, V, W, nbest, blank)
+        return ids, ids_len, scores
+    ctc_scores, lm_scores = torch.empty_like(scores), torch.empty_like(scores)
+    N.call("v100_ctc_beam_search_lm", logits, lens, ws, ids, ids_len, scores, logp, nxt, fin, S, int(lm.start), alpha, beta,
+           int(bool(use_eos)), ctc_scores, lm_scores, B, T, V, W, nbest, blank)
+    return ids, ids_len, scores, ctc_scores, lm_scores

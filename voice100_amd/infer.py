@@ -210,14 +210,26 @@ class ASRPipeline:
     -> greedy CTC ids [B, T'] int64 (zero padded) + lengths (data_modules.py:276-291, asr.py:110-116, text.py:99-104).
     beam_size=W decodes with the CTC prefix beam search instead (K24; no counterpart in the reference): the call returns its best
     hypothesis in the same form, so transcribe, score and evaluate work unchanged, and nbest() returns the `nbest` best with scores.
+    lm=<a compiled lm.NGramLM on the model's device> fuses it into that search (K25): hypotheses are ranked by
+    log p_ctc + lm_weight * log p_lm + length_bonus * length, and nbest() returns (ids, lens, scores, ctc_scores, lm_scores).
 
     With `lengths` the rows are utterances of their own lengths: samples per row when the pipeline has a `mel` (the features
     and their frame counts then come from one ragged launch, mel.transform(wav, lengths)), frames per row when it has none
     (wav_or_mel is the padded feature batch); the decode stops at model.output_length(frames) of each row."""
 
-    def __init__(self, model, mel=None, beam_size=None, nbest=1):
+    def __init__(self, model, mel=None, beam_size=None, nbest=1, lm=None, lm_weight=0.5, length_bonus=0.0):
+        if lm is not None and beam_size is None:
+            raise RuntimeError("ASRPipeline: a language model needs a beam_size (the greedy decode has nothing to rank)")
         self.model, self.mel = model, mel
         self.beam_size, self.nbest_size = beam_size, nbest     # beam_size=None: the greedy decode
+        self.lm, self.lm_weight, self.length_bonus = lm, lm_weight, length_bonus
+
+    def _beam(self, logits, out_len, nbest):
+        from .decode import ctc_beam_search
+        if self.lm is None:
+            return ctc_beam_search(logits, out_len, self.beam_size, nbest)
+        return ctc_beam_search(logits, out_len, self.beam_size, nbest, lm=self.lm, lm_weight=self.lm_weight,
+                               length_bonus=self.length_bonus)
 
     def _logits(self, wav_or_mel: torch.Tensor, lengths=None):
         """The model's logits and, with `lengths`, the output frames of each row (else None)."""
@@ -234,22 +246,22 @@ class ASRPipeline:
     def __call__(self, wav_or_mel: torch.Tensor, lengths=None):
         """(ids [B, T'] int64 zero padded, lens [B] int32): the greedy decode, or with a beam_size the best hypothesis of the prefix
         beam search (decode.ctc_beam_search, K24)."""
-        from .decode import ctc_beam_search, ctc_greedy_decode
+        from .decode import ctc_greedy_decode
         logits, out_len = self._logits(wav_or_mel, lengths)
         if self.beam_size is None:
             return ctc_greedy_decode(logits) if out_len is None else ctc_greedy_decode(logits, out_len)
-        ids, n, _ = ctc_beam_search(logits, out_len, self.beam_size, 1)
+        ids, n = self._beam(logits, out_len, 1)[:2]
         return ids[:, 0], n[:, 0]
 
     @torch.no_grad()
     def nbest(self, wav_or_mel: torch.Tensor, lengths=None):
         """The nbest hypotheses of the beam search, best first: (ids [B, nbest, T'] int64 zero padded, lens [B, nbest] int32,
-        scores [B, nbest] fp32 = total log probability; -inf with length 0 where there are fewer hypotheses).  Needs a beam_size."""
-        from .decode import ctc_beam_search
+        scores [B, nbest] fp32 = total log probability; -inf with length 0 where there are fewer hypotheses), and with a language model
+        also ctc_scores and lm_scores [B, nbest] fp32 (scores is then the fused score).  Needs a beam_size."""
         if self.beam_size is None:
             raise RuntimeError("ASRPipeline.nbest: the pipeline was built without a beam_size (the greedy decode has one hypothesis)")
         logits, out_len = self._logits(wav_or_mel, lengths)
-        return ctc_beam_search(logits, out_len, self.beam_size, self.nbest_size)
+        return self._beam(logits, out_len, self.nbest_size)
 
     def transcribe(self, paths, decode: Callable[[torch.Tensor], str]) -> List[str]:
         """WAV files -> their transcripts: audio_io.load_batch, the ragged pipeline, then `decode` (the caller's tokenizer.decode,
