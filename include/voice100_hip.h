@@ -240,7 +240,7 @@ int v100_exp_clip(const float* x, float* y, float offset, long long n, void* str
  *                            by the caller -> y [B][Ymax] fp32, Ymax = (int)(T * frame_period_ms * fs / 1000), zero beyond
  *                            an utterance's own length; n_pulses [B] (-1 and a NaN row: more than max_pulses pulses). */
 /* ---- channel-major inference layout (round 4; csrc/block.hip v100_ir_fwd_eval with shape[10] == 2) --------------------------
- * Activations [C][B][P], P = (T + 7) & ~7: one [C x (B P)] matrix with every utterance's (padded) row back to back, so a 1x1
+ * Activations [C][B][P], P = v100_row_pitch16(T, B): one [C x (B P)] matrix with every utterance's (padded) row back to back, so a 1x1
  * convolution is ONE GEMM over all B P columns (asr.py:47,51 on 1-second chunks: full 128-column tiles instead of 51 of 128) and a
  * channel's rows are contiguous for the depthwise kernel.  Block inputs / outputs fp32, hidden tensors in the GEMM operand format
  * (bf16, or fp16 at precision "fp16").  v100_bct_to_cm: [B][C][T] fp32 -> [C][B][P] (padding zeroed); v100_cm_to_btc: [C][B][P] ->
@@ -312,8 +312,9 @@ int v100_rows_copy_probe(const void* src, void* dst, int B, int C, int row_bytes
  * In bf16 mode the reference under autocast keeps its conv activations in bf16; here the two tensors a block saves for
  * backward (a1 = expand output, a2 = depthwise output, each 4x the block's width) and optionally the two hidden gradients
  * (act16 level 2; level 3 adds the project output a3, saved for backward, and its gradient da3; level 4 a bf16 shadow of the block
- * output for the next block's X operand, v100_chan_affine2_shadow) are stored as bf16 [B][C][P], P = (T + 7) & ~7 (pitched rows: every 4- / 8-sample access stays 8 / 16-byte aligned for any
- * T).  Accumulators, BatchNorm statistics and reductions stay fp32.  io16 masks select which operands are such tensors:
+ * output for the next block's X operand, v100_chan_affine2_shadow) are stored as bf16 [B][C][P], P = v100_row_pitch16(T, B) (pitched rows: every 4- / 8-sample access stays 8 / 16-byte aligned for any
+ * T).  Callers must size every such tensor with v100_row_pitch16: the kernels address rows by it, and a tensor sized by another
+ * rule is written out of bounds.  Accumulators, BatchNorm statistics and reductions stay fp32.  io16 masks select which operands are such tensors:
  *   v100_pw_gemm_io:   1 X, 2 X2, 4 Y, 8 R        v100_pw_wgrad_io: 1 G, 2 G2, 4 X
  *   v100_dwconv_*_io:  1 x (first stream), 2 x2, 4 aux (a1), 8 y; 16 = the tensors are CHANNEL-MAJOR [C][B][P] (rows of up to 768
  *                      outputs; the layout probe of round 4: tools/bench_dw_regimes.py --cm, tests/test_gpu_act16.py)
@@ -377,7 +378,7 @@ int v100_dwconv_fwd_eval_io(const void* h1, const float* w, const float* out_a, 
  * of v100_chan_affine2_io: 1 = u is bf16 (y = s3*a3 + t3 (+ x)), 6 = v and out are bf16 (da3 = p*dy + q*a3 + r) */
 int v100_chan_reduce2_io(const void* u, const void* v, float* partial, int G, int B, int C, int T, int io16, void* stream);
 /* the forward block output (asr.py:55-59) with a bf16 shadow beside it (act16 level 4): out = A*u + Cc (+ v) as fp32 [B][C][T] AND
- * rounded to bf16 in shadow [B][C][(T + 7) & ~7]; u is bf16 (pitched) when u_bf16, else fp32.  The shadow is what the NEXT block's
+ * rounded to bf16 in shadow [B][C][v100_row_pitch16(T, B)]; u is bf16 (pitched) when u_bf16, else fp32.  The shadow is what the NEXT block's
  * expand GEMM / expand weight gradient read as X (io16 bit PW_IO_X / WG_IO_X): same results, half the operand bytes. */
 int v100_chan_affine2_shadow(const void* u, const float* v, const float* A, const float* Cc, float* out, void* shadow,
                              int B, int C, int T, int u_bf16, void* stream);
@@ -438,14 +439,26 @@ int v100_ctc_loss_mean_t(const float* logits, const long long* targets, const in
                          float* nll, float* loss, float* grad, int grad_bvt, int B, int T, int V, int Lmax, int blank, void* stream);
 
 /* ---- block executor (csrc/block.hip): the whole kernel chain of one InvertedResidual block (asr.py:40-59) per call.
- * shape = {B, Cin, hid, Cout, T, K, stride, residual, bf16, prepped, act16} (11 ints; act16: see "act16" above -- then the
- * caller passes a1 / a2 as bf16 [B][hid][(T+7)&~7]); coef = 12 vectors of `hid` floats (BN scale/shift/mean/rstd
- * of the three BatchNorms) written by forward and read by backward.  Pointer tables (device pointers unless noted):
+ * shape = {B, Cin, hid, Cout, T, K, stride, residual, bf16, flags, act16} (11 ints; act16: see "act16" above -- then the
+ * caller passes a1 / a2 as bf16 [B][hid][v100_row_pitch16(T, B)]); coef = 12 vectors of max(hid, Cout) floats (BN
+ * scale/shift/mean/rstd of the three BatchNorms) written by forward and read by backward.  flags = an OR of the three V100_IR_*
+ * bits below; every other bit is reserved to the stack executor and must be 0.
+ * Pointer tables (device pointers unless noted):
  *  fwd: x | w1 g1 b1 rm1 rv1 nbt1 | wd g2 b2 rm2 rv2 nbt2 | w3 g3 b3 rm3 rv3 nbt3 | a1 a2 a3 y coef workspace prep   (26)
+ *       | x16 y16 (28: only with V100_IR_SHADOW_SLOTS; each may be NULL): the bf16 shadow [B][C][v100_row_pitch16(T, B)] of x
+ *       (written by the previous block) and of y (for the next block), read at act16 level >= 4
  *  bwd: x a1 a2 a3 | w1 wd w3 | g1 g2 g3 | coef | dy | dx (NULL = skip) | dW1 dg1 db1 dWd dg2 db2 dW3 dg3 db3 | workspace prep (24)
- * prep = v100_ir_prep_bytes(shape) bytes: bf16 / transposed weight copies written by forward (unless shape.prepped: the
- * caller has filled it, e.g. with v100_ir_prep_batched for the n <= 32 blocks of a stack in one launch; shapes = n x 10
+ *       | x16 (25: only with V100_IR_SHADOW_SLOTS; may be NULL) | the block's region for deferred weight gradients (26: read
+ *       only with the stack executor's reserved defer bit, never by a caller of this header)
+ * prep = v100_ir_prep_bytes(shape) bytes: bf16 / transposed weight copies written by forward (unless V100_IR_PREPPED: the
+ * caller has filled it, e.g. with v100_ir_prep_batched for the n <= 32 blocks of a stack in one launch; shapes = n x 11
  * ints) and reused by backward.  `shape(s)` and the tables are HOST arrays. */
+enum {
+    V100_IR_PREPPED = 1,        /* prep is filled already: forward does not prepare the weights */
+    V100_IR_SHADOW_SLOTS = 2,   /* the pointer tables carry the x16 / y16 slots */
+    V100_IR_FROZEN = 8          /* BatchNorm normalises with its running statistics and updates nothing (a block in eval() that
+                                 * takes part in autograd); act16 must be 0 */
+};
 long long v100_ir_prep_bytes(const int* shape);
 long long v100_ir_fwd_workspace_bytes(const int* shape);
 /* eval mode (inference): folded BatchNorm coefficients + bf16 weight copies in a caller-owned cache (refill with
@@ -473,7 +486,7 @@ int v100_ir_bwd(const int* shape, const void* const* ptrs, void* stream);
  * blob_bytes (-1: bad descriptor).  The caller allocates the blob (kept until backward), the backward workspace and the gradient
  * buffer: grad_floats floats, per block dW1 dg1 db1 dWd dg2 db2 dW3 dg3 db3.
  * params (HOST pointer table, 18 per block): w1 g1 b1 rm1 rv1 nbt1 | wd g2 b2 rm2 rv2 nbt2 | w3 g3 b3 rm3 rv3 nbt3.
- * x16 (may be NULL): bf16 shadow [B][cin][(T + 7) & ~7] of x (act16 level 4). */
+ * x16 (may be NULL): bf16 shadow [B][cin][v100_row_pitch16(T, B)] of x (act16 level 4). */
 long long v100_ir_stack_plan(const int* desc, long long* plan);
 int v100_ir_stack_fwd_train(const int* desc, const void* const* params, const void* x, const void* x16, void* blob, void* stream);
 int v100_ir_stack_bwd(const int* desc, const void* const* params, const void* x, const void* x16, const void* blob, const void* dy,

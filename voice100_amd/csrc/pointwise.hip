@@ -18,6 +18,7 @@
 // 1-D grid with an XCD-aware remap: the M-tiles that share one X tile run on one XCD (one L2).
 #include "pointwise_common.h"
 #include "timing.h"
+#include "block_shape.h"        // IrPrep: where v100_ir_prep_batched writes the copies
 
 void pw_launch_gemm_f32(const PwParams& p, dim3 grid, hipStream_t st);
 void pw_launch_gemm_bf16(const PwParams& p, dim3 grid, hipStream_t st);
@@ -106,6 +107,98 @@ extern "C" int v100_weight_prep_f16(const float* w, int rows, int cols, void* w1
     const long n = (long)rows * cols;
     V100_GGL(weight_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, rows, cols,
                        (u16*)w16, (float*)nullptr, (u16*)nullptr, 1);
+    return v100_launch_status();
+}
+
+// Prepared weights of n blocks in ONE launch (the per-block pair of weight_prep launches costs ~13 us a block, mostly
+// launch latency).  shapes: n x IR_NSHAPE ints; w1s / w3s: the fp32 weights; preps: each block's prep buffer.  HOST arrays.
+struct PrepBatch {
+    enum { MAXN = 32 };
+    const float* w[2 * MAXN]; u16* wbf[2 * MAXN]; float* wt[2 * MAXN]; u16* wtbf[2 * MAXN];
+    int rows[2 * MAXN], cols[2 * MAXN];
+};
+// 64 x 64 tiles through LDS: the row-major bf16 copy and BOTH transposed copies are written in full lines (the element-wise
+// form scattered the transposed copies 2 / 4 bytes at a time: 58 us per step for 46 MB of weights).
+__global__ __launch_bounds__(256) void weight_prep_batched_kernel(PrepBatch t) {
+    __shared__ float tile[64][65];
+    const int e = blockIdx.y;
+    const float* __restrict__ w = t.w[e];
+    const int rows = t.rows[e], cols = t.cols[e];
+    const int tr = (rows + 63) >> 6, tc = (cols + 63) >> 6;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;            // 64 columns x 4 row groups
+    // Whole 64 x 64 tiles of a bf16-only preparation (every 1x1 weight of the step's networks): 16-byte loads, 8-byte packed stores on
+    // both copies (the element-wise form below moved the transposed copy 2 bytes per lane: 30.7 us for the step's 86.7 MB, 2.8 TB/s).
+    const bool fast = !(rows & 63) && !(cols & 63) && t.wt[e] == nullptr && t.wbf[e] != nullptr && t.wtbf[e] != nullptr;
+    for (int tl = blockIdx.x; fast && tl < tr * tc; tl += gridDim.x) {
+        const int r0 = (tl / tc) << 6, c0 = (tl % tc) << 6;
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int id = threadIdx.x + 256 * q;                      // 64 rows x 16 float4
+            const int i = id >> 4, c4 = (id & 15) << 2;
+            const f32x4 v = *reinterpret_cast<const f32x4*>(w + (size_t)(r0 + i) * cols + c0 + c4);
+            uint2 o; o.x = pack_bf16(v[0], v[1]); o.y = pack_bf16(v[2], v[3]);
+            *reinterpret_cast<uint2*>(t.wbf[e] + (size_t)(r0 + i) * cols + c0 + c4) = o;
+            tile[i][c4] = v[0]; tile[i][c4 + 1] = v[1]; tile[i][c4 + 2] = v[2]; tile[i][c4 + 3] = v[3];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int id = threadIdx.x + 256 * q;                      // 64 columns x 16 groups of 4 rows
+            const int c = id >> 4, r4 = (id & 15) << 2;
+            uint2 o; o.x = pack_bf16(tile[r4][c], tile[r4 + 1][c]); o.y = pack_bf16(tile[r4 + 2][c], tile[r4 + 3][c]);
+            *reinterpret_cast<uint2*>(t.wtbf[e] + (size_t)(c0 + c) * rows + r0 + r4) = o;
+        }
+    }
+    for (int tl = blockIdx.x; !fast && tl < tr * tc; tl += gridDim.x) {
+        const int r0 = (tl / tc) << 6, c0 = (tl % tc) << 6;
+        __syncthreads();                                               // the previous tile's reads are done
+#pragma unroll 4
+        for (int i = ty; i < 64; i += 4) {
+            const int r = r0 + i, c = c0 + tx;
+            float v = 0.f;
+            if (r < rows && c < cols) {
+                v = w[(size_t)r * cols + c];
+                if (t.wbf[e]) t.wbf[e][(size_t)r * cols + c] = f2bf(v);
+            }
+            tile[i][tx] = v;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int i = ty; i < 64; i += 4) {
+            const int c = c0 + i, r = r0 + tx;                         // transposed: consecutive threads walk the ROWS of w
+            if (c < cols && r < rows) {
+                const float v = tile[tx][i];
+                if (t.wt[e]) t.wt[e][(size_t)c * rows + r] = v;
+                if (t.wtbf[e]) t.wtbf[e][(size_t)c * rows + r] = f2bf(v);
+            }
+        }
+    }
+}
+extern "C" int v100_ir_prep_batched(const int* shapes, const void* const* w1s, const void* const* w3s, void* const* preps, int n,
+                                    void* stream) {
+    if (!shapes || !w1s || !w3s || !preps) return V100_ERR_NULL;
+    if (n <= 0 || n > PrepBatch::MAXN) return V100_ERR_SHAPE;
+    PrepBatch t;
+    long maxn = 0;
+    for (int i = 0; i < n; ++i) {
+        const int* sh = shapes + (size_t)i * IR_NSHAPE;
+        if (!w1s[i] || !w3s[i] || !preps[i]) return V100_ERR_NULL;
+        IrPrep pw;
+        ir_prep_carve(ir_shape(sh, false), preps[i], pw);
+        t.w[2 * i] = (const float*)w1s[i]; t.rows[2 * i] = sh[IR_HID]; t.cols[2 * i] = sh[IR_CIN];
+        t.wbf[2 * i] = (u16*)pw.w1bf; t.wt[2 * i] = pw.w1t; t.wtbf[2 * i] = (u16*)pw.w1tbf;
+        t.w[2 * i + 1] = (const float*)w3s[i]; t.rows[2 * i + 1] = sh[IR_COUT]; t.cols[2 * i + 1] = sh[IR_HID];
+        t.wbf[2 * i + 1] = (u16*)pw.w3bf; t.wt[2 * i + 1] = pw.w3t; t.wtbf[2 * i + 1] = (u16*)pw.w3tbf;
+        const long a = (long)sh[IR_HID] * sh[IR_CIN], b = (long)sh[IR_COUT] * sh[IR_HID];
+        if (a > maxn) maxn = a;
+        if (b > maxn) maxn = b;
+        if (a <= 0 || b <= 0) return V100_ERR_SHAPE;
+    }
+    long gx = (maxn + 4095) / 4096;           // 64 x 64 tiles of the largest matrix
+    if (gx > 256) gx = 256;
+    if (gx < 1) gx = 1;
+    V100_GGL(weight_prep_batched_kernel, dim3((unsigned)gx, 2 * n), dim3(256), 0, (hipStream_t)stream, t);
     return v100_launch_status();
 }
 

@@ -214,6 +214,29 @@ def _ptr_table(items):
     return arr
 
 
+# The block executor's shape array (include/voice100_hip.h): where its flags and act16 level sit, and the three public flag bits
+_SH_FLAGS, _SH_ACT16 = 9, 10
+_IR_PREPPED, _IR_SHADOW_SLOTS, _IR_FROZEN = 1, 2, 8
+# Of a block's 18 parameter / buffer slots (_block_tensors), the nine trainable ones -- w1 g1 b1 wd g2 b2 w3 g3 b3: the order of the
+# executors' gradients -- and the nine running-statistics buffers
+_TRAINABLE_SLOTS = (0, 1, 2, 6, 7, 8, 12, 13, 14)
+_STAT_SLOTS = (3, 4, 5, 9, 10, 11, 15, 16, 17)
+
+
+def _block_grad_sizes(cin, hid, cout, k):
+    """Element counts of a block's nine gradients, in the order the executors lay them out: dW1 dg1 db1 dWd dg2 db2 dW3 dg3 db3."""
+    return (hid * cin, hid, hid, hid * k, hid, hid, cout * hid, cout, cout)
+
+
+def _block_grad_views(flat, off, sizes):
+    """The nine gradients of one block as views of the flat buffer from element `off`; returns (views, the offset behind them)."""
+    views = []
+    for numel in sizes:
+        views.append(flat[off:off + numel])
+        off += numel
+    return views, off
+
+
 class InvertedResidualTrainFn(torch.autograd.Function):
     """Training-mode InvertedResidual (asr.py:40-59): batch statistics, running-stat update, autograd.
     Forward and backward are ONE call each into the library's block executor (csrc/block.hip), which
@@ -224,7 +247,7 @@ class InvertedResidualTrainFn(torch.autograd.Function):
                 kernel_size, stride, use_residual, precision, prep=None, x16=None, want_shadow=False, frozen=False):
         # frozen: the block is in eval() but inside autograd (partial-freeze fine-tuning; an eval-mode model called without no_grad):
         # BatchNorm normalises with its RUNNING statistics, updates nothing, and back-propagates through that fixed affine -- what
-        # nn.BatchNorm1d does in eval mode (asr.py:36,52).  Runs on the executor's fp32-storage path (shape[9] bit 3).
+        # nn.BatchNorm1d does in eval mode (asr.py:36,52).  Runs on the executor's fp32-storage path (_IR_FROZEN).
         _check(x, "InvertedResidual")
         x = x.contiguous()
         B, cin, T = x.shape
@@ -233,12 +256,12 @@ class InvertedResidualTrainFn(torch.autograd.Function):
         T2 = conv_out_len(T, k, stride)
         bf16 = _fmt(precision)
         _no_fp16_training(bf16, "InvertedResidual (training mode)")
-        # shape[9]: bit 0 = weights prepared by the stack, bit 1 = the pointer table carries the bf16-shadow slots (level 4)
+        # flags: the weights are prepared already (by the stack), the pointer table carries the bf16-shadow slots (level 4)
         shadows = bf16 == 1 and _ACT16 >= 4 and not frozen
-        shape = (ctypes.c_int * 11)(B, cin, hid, cout, T, k, int(stride), int(bool(use_residual)), int(bf16),
-                                    int(prep is not None) | (2 if shadows else 0) | (8 if frozen else 0), 0)
+        flags = (_IR_PREPPED if prep is not None else 0) | (_IR_SHADOW_SLOTS if shadows else 0) | (_IR_FROZEN if frozen else 0)
+        shape = (ctypes.c_int * 11)(B, cin, hid, cout, T, k, int(stride), int(bool(use_residual)), int(bf16), flags, 0)
         if bf16 == 1 and _ACT16 and not frozen and N.helper("v100_ir_act16_supported", shape):
-            shape[10] = _ACT16
+            shape[_SH_ACT16] = _ACT16
             pitch = pitch16(T, B)                      # bf16 rows are pitched (aligned 8 / 16-byte accesses; long rows on 128-byte lines)
             a1 = torch.empty((B, hid, pitch), dtype=torch.bfloat16, device=x.device)
             a2 = torch.empty((B, hid, pitch), dtype=torch.bfloat16, device=x.device)
@@ -251,7 +274,7 @@ class InvertedResidualTrainFn(torch.autograd.Function):
         # level 4: a bf16 copy of y (pitched rows) for the next block's expand GEMM / expand weight gradient; x16 = the copy
         # of x the previous block wrote (only the act16 executor reads it)
         y16 = torch.empty((B, cout, pitch16(T2, B)), dtype=torch.bfloat16, device=x.device) if (shadows and want_shadow) else None
-        if not (shadows and shape[10] >= 4):
+        if not (shadows and shape[_SH_ACT16] >= 4):
             x16 = None
         coef = _f32(12, max(hid, cout), like=x)
         ws = torch.empty(N.helper("v100_ir_fwd_workspace_bytes", shape), dtype=torch.uint8, device=x.device)
@@ -288,16 +311,12 @@ class InvertedResidualTrainFn(torch.autograd.Function):
         dy = dy.contiguous()
         hid, cin = w1.shape[0], w1.shape[1]
         cout, k = w3.shape[0], wd.shape[2]
-        # parameter gradients in one allocation: dW1 dg1 db1 dWd dg2 db2 dW3 dg3 db3
-        sizes = (hid * cin, hid, hid, hid * k, hid, hid, cout * hid, cout, cout)
-        flat = _f32(sum(sizes), like=x)
-        parts, off = [], 0
-        for n in sizes:
-            parts.append(flat[off:off + n])
-            off += n
+        # parameter gradients in one allocation
+        sizes = _block_grad_sizes(cin, hid, cout, k)
+        parts, _ = _block_grad_views(_f32(sum(sizes), like=x), 0, sizes)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         ws = torch.empty(N.helper("v100_ir_bwd_workspace_bytes", shape), dtype=torch.uint8, device=x.device)
-        extra = (x16,) if (shape[9] & 2) else ()
+        extra = (x16,) if (shape[_SH_FLAGS] & _IR_SHADOW_SLOTS) else ()
         N.call("v100_ir_bwd", shape, _ptr_table((x, a1, a2, a3, w1, wd, w3, g1, g2, g3, coef, dy, dx) + tuple(parts) + (ws, prep) + extra))
         dW1, dg1, db1, dWd, dg2, db2, dW3, dg3, db3 = parts
         return (dx, dW1.view_as(w1), dg1, db1, dWd.view_as(wd), dg2, db2, dW3.view_as(w3), dg3, db3) + (None,) * 17
@@ -412,7 +431,7 @@ class IRStackTrainFn(torch.autograd.Function):
         blob = torch.empty(totals[0], dtype=torch.uint8, device=x.device)
         ptab = (ctypes.c_void_p * (18 * n))(*[t.data_ptr() for t in params])
         N.call("v100_ir_stack_fwd_train", desc, ptab, x, x16, blob)
-        _touched([params[18 * i + j] for i in range(n) for j in (3, 4, 5, 9, 10, 11, 15, 16, 17)])     # the blocks' running statistics
+        _touched([params[18 * i + j] for i in range(n) for j in _STAT_SLOTS])     # the blocks' running statistics
         o = blocks[-1]
         cout, T2 = cfgs[-1][2], o[7]
         y = blob[o[3]:o[3] + 4 * B * cout * T2].view(torch.float32).view(B, cout, T2)
@@ -440,7 +459,7 @@ class IRStackTrainFn(torch.autograd.Function):
             dy = torch.zeros(ctx.y_shape, dtype=torch.float32, device=x.device)
         dy = dy.contiguous()
         # under data parallelism the gradients are written straight into the exchange buffer (no packing copy): same values, another home
-        weights = [params[18 * b + j] for b in range(n) for j in (0, 1, 2, 6, 7, 8, 12, 13, 14)]
+        weights = [params[18 * b + j] for b in range(n) for j in _TRAINABLE_SLOTS]
         grads = _grad_arena_for(weights, totals[2]) if _GRAD_ARENAS else None
         if grads is None:
             grads = _f32(totals[2], like=x)
@@ -450,10 +469,8 @@ class IRStackTrainFn(torch.autograd.Function):
         ctx.blob = None                                   # the activations are dead: free them before the rest of backward runs
         out, off = [], 0
         for i, (cin, hid, cout, k, _, _) in enumerate(cfgs):
-            p = params[18 * i:18 * i + 18]
-            for j, numel in ((0, hid * cin), (1, hid), (2, hid), (6, hid * k), (7, hid), (8, hid), (12, cout * hid), (13, cout), (14, cout)):
-                out.append(grads[off:off + numel].view_as(p[j]))
-                off += numel
+            views, off = _block_grad_views(grads, off, _block_grad_sizes(cin, hid, cout, k))
+            out += [v.view_as(params[18 * i + j]) for v, j in zip(views, _TRAINABLE_SLOTS)]
         return (dx, None, None) + tuple(out)
 
 
@@ -529,7 +546,7 @@ def ir_stack_train(blocks, x, precision: Optional[str] = None, segment: Optional
         x16 = sh[0] if (sh is not None and sh[1] == x._version and sh[0].shape[:2] == x.shape[:2]
                         and sh[0].shape[2] == pitch16(x.shape[2], x.shape[0])) else None
         last = i + 1 == len(segs)
-        weights = [params[18 * b + j] for b in range(len(cfgs)) for j in (0, 1, 2, 6, 7, 8, 12, 13, 14)]
+        weights = [params[18 * b + j] for b in range(len(cfgs)) for j in _TRAINABLE_SLOTS]
         y, y16 = IRStackTrainFn.apply(x, x16, (cfgs, precision, not last, params), *weights)
         if y16 is not None:
             y._v100_shadow = (y16, y._version)
@@ -608,7 +625,7 @@ def inverted_residual_eval_cached(blk, x, precision: Optional[str] = None):
     if bf16 == 1 and _ACT16 and N.helper("v100_ir_act16_supported", shape):
         # precision "bf16": the two hidden tensors (4x the block's width, values in [0, 6] after BatchNorm + ReLU6) stored as bf16 with
         # pitched rows -- half the bytes of the big streams of all three kernels (the GEMMs round them to bf16 as operands anyway)
-        shape[10] = 1
+        shape[_SH_ACT16] = 1
         pitch = pitch16(T, B)
         h1 = torch.empty((B, hid, pitch), dtype=torch.bfloat16, device=x.device)
         h2 = torch.empty((B, hid, pitch), dtype=torch.bfloat16, device=x.device)
@@ -689,7 +706,7 @@ def inverted_residual_eval_cm(blk, x: torch.Tensor, B: int, T: int, precision: O
         cache = torch.empty(N.helper("v100_ir_eval_cache_bytes", shape), dtype=torch.uint8, device=x.device)
         N.call("v100_ir_eval_prep", shape, _ptr_table(tuple(t.detach() for t in params) + (cache,)))
         blk._eval_cache, blk._eval_key = cache, key
-    shape[10] = 2
+    shape[_SH_ACT16] = 2
     h = torch.empty((2, hid, B * P), dtype=torch.float16 if fmt == 2 else torch.bfloat16, device=x.device)
     y = _f32(cout, B * P, like=x)
     N.call("v100_ir_fwd_eval", shape, _ptr_table((x, w1.detach(), wd.detach(), w3.detach(), blk._eval_cache, h[0], h[1], y)))
@@ -739,7 +756,7 @@ def ir_stack_eval_cm(blocks, x: torch.Tensor, B: int, T: int, precision: Optiona
             shape = (ctypes.c_int * 11)(B, cin, hid, cout, T, k, 1, int(bool(blk.use_residual)), int(fmt), 0, 0)
             cache = torch.empty(N.helper("v100_ir_eval_cache_bytes", shape), dtype=torch.uint8, device=x.device)
             N.call("v100_ir_eval_prep", shape, _ptr_table(tuple(t.detach() for t in params) + (cache,)))
-            shape[10] = 2
+            shape[_SH_ACT16] = 2
             for j in range(11):
                 plan.shapes[11 * i + j] = shape[j]
             plan.ptrs[8 * i + 1], plan.ptrs[8 * i + 2], plan.ptrs[8 * i + 3] = w1.data_ptr(), wd.data_ptr(), w3.data_ptr()
