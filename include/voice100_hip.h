@@ -564,6 +564,30 @@ int v100_ctc_beam_search_lm(const float* logits, const int* lens, void* ws, long
                             const float* lm_logp, const int* lm_next, const float* lm_final, int S, int start_state, float alpha,
                             float beta, int use_eos, float* ctc_scores, float* lm_scores, int B, int T, int V, int W, int nbest,
                             int blank, void* stream);
+/* K26, word timestamps and confidences (csrc/ctc_segment.hip): the CTC forward-backward over all alignments of a GIVEN transcript
+ * in one launch, reduced per label and per word.  It is the posterior of the alignments given the transcript, not a posterior of
+ * the transcript being right.  logits [B][T][V] fp32 (the kernel takes the log-softmax itself), labels [B][Lmax] int64; in_len /
+ * lab_len [B] int32 or NULL (= T / Lmax everywhere), clamped to [0, T] / [0, Lmax] on the device; nothing beyond a row's lengths is
+ * read.  With gamma_t(i) the posterior probability that frame t is spent in label i:
+ *   log_prob [B]           log p(labels | logits), the sum over all alignments (= -nll of K10, K24's score of that transcript)
+ *   duration [B][Lmax]     sum_t gamma_t(i), the expected number of frames
+ *   log_conf [B][Lmax]     sum_t gamma_t(i) log_softmax(logits[t])[l_i] / duration[i]
+ *   start, end [B][Lmax]   the medians of the label's first frame and of one past its last frame: start < end <= next start <= T_b
+ * and per word, a maximal run of labels != sep inside the row's length ([B][(Lmax + 1) / 2]): word_first (its first label), word_count,
+ * word_start = start[first], word_end = end[last], word_log_conf = the same ratio over the word's labels; n_words [B].  The six word
+ * pointers are all NULL (no word level) or all given.  Beyond lab_len / n_words everything is 0.  An infeasible row (p = 0: too few
+ * frames, a label equal to blank or outside [0, V)) gets log_prob -inf and start = end = 0, duration 0, log_conf -inf for its labels
+ * and words; T_b = 0 gives log_prob 0 iff the row has no label.  No float atomics: two calls give equal bits.
+ * ws: v100_ctc_segment_workspace_bytes(B, T, Lmax) bytes (-1 = unsupported shape).  v100_ctc_segment_block(): frames per staged block
+ * of emissions (lengths around it and its multiples are the kernel's seams).
+ * B >= 1, 1 <= T <= 4096, 2 <= V <= 128, 1 <= Lmax <= 2047, 0 <= blank < V, else 1; a NULL required pointer, or some but not all of
+ * the word pointers, 3; both before anything touches a device. */
+long long v100_ctc_segment_workspace_bytes(int B, int T, int Lmax);
+int v100_ctc_segment_block(void);
+int v100_ctc_segment(const float* logits, const int* in_len, const long long* labels, const int* lab_len, void* ws, float* log_prob,
+                     int* start, int* end, float* duration, float* log_conf, int* word_first, int* word_count, int* word_start,
+                     int* word_end, float* word_log_conf, int* n_words, int B, int T, int V, int Lmax, int blank, long long sep,
+                     void* stream);
 /* TextToAlignTextModel.align (voice100/models/tts.py:89-110) batched: text [B][Lmax] int64, align [B][Lmax][2] float64
  * (gap, length), out [B][Tmax] int64 (zero padded; rows longer than Tmax are cut), out_len [B].  out == NULL: only out_len is
  * written (head + int(sum(align)) + tail per utterance), so the caller can size `out` with one read-back. */

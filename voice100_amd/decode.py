@@ -5,8 +5,10 @@ score, voice100/align_text.py:39-56), TextToAlignTextModel.align (voice100/model
 TextToAlignText.align (voice100/models/_align_v2.py:48-73).  edit_distance (K23) has no counterpart in the reference: it scores decoded
 ids against reference ids (character / phone and word error counts) without leaving the device.  Neither has ctc_beam_search (K24):
 the CTC prefix beam search, n best transcripts with their total log probabilities, where the reference decodes greedily, nor its
-fused form (K25): the same search with an lm.NGramLM voting inside every frame's selection."""
+fused form (K25): the same search with an lm.NGramLM voting inside every frame's selection, nor ctc_segment (K26): the CTC
+forward-backward over the alignments of a given transcript, reduced to time boundaries, durations and confidences per label and word."""
 import math
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -221,3 +223,70 @@ def ctc_beam_search(logits: torch.Tensor, lengths: torch.Tensor = None, beam_siz
     N.call("v100_ctc_beam_search_lm", logits, lens, ws, ids, ids_len, scores, logp, nxt, fin, S, int(lm.start), alpha, beta,
            int(bool(use_eos)), ctc_scores, lm_scores, B, T, V, W, nbest, blank)
     return ids, ids_len, scores, ctc_scores, lm_scores
+
+
+class CTCSegments(NamedTuple):
+    """What ctc_segment returns; the word fields are None with sep=None."""
+    log_prob: torch.Tensor                               # [B] fp32: log p(labels | logits), summed over all alignments
+    start: torch.Tensor                                  # [B, L] int32: the median first frame of each label
+    end: torch.Tensor                                    # [B, L] int32: one past the median last frame
+    duration: torch.Tensor                               # [B, L] fp32: the expected number of frames
+    log_confidence: torch.Tensor                         # [B, L] fp32: occupancy-weighted mean log posterior of the label
+    word_first: Optional[torch.Tensor]                   # [B, (L + 1) // 2] int32: index of the word's first label
+    word_count: Optional[torch.Tensor]                   # ... its number of labels
+    word_start: Optional[torch.Tensor]                   # ... start of its first label
+    word_end: Optional[torch.Tensor]                     # ... end of its last label
+    word_log_confidence: Optional[torch.Tensor]          # ... fp32: the same mean over all the word's labels
+    n_words: Optional[torch.Tensor]                      # [B] int32
+
+
+def ctc_segment(logits: torch.Tensor, lengths: torch.Tensor, labels: torch.Tensor, label_lengths: torch.Tensor, blank: int = 0,
+                sep=1) -> CTCSegments:
+    """Time boundaries, expected durations and confidences of every label and word of a GIVEN transcript, from the CTC
+    forward-backward over all its alignments in one launch (K26, csrc/ctc_segment.hip): logits [B, T, V] fp32 (the model's output; the
+    kernel normalises), lengths [B] or None, labels [B, L] int64 (any hypothesis: a reference text, a decode), label_lengths [B] or
+    None -> CTCSegments of device tensors.  No read-back inside the call.
+
+    This is the posterior of the ALIGNMENTS given the transcript -- when each label was spoken if the transcript is right, and how
+    well the frames it claims support it -- not a posterior of the transcript being right.  With gamma_t(i) the posterior probability
+    that frame t is spent in label i: duration = sum_t gamma_t(i), log_confidence = sum_t gamma_t(i) log_softmax(logits[t])[l_i] /
+    duration (exp of it is the confidence), start / end = the medians of the label's first frame and of one past its last frame, so
+    start < end <= the next label's start.  A word is a maximal run of labels != sep (edit_distance's rule); sep=None: no word level.
+    Lengths are clamped to [0, T] / [0, L] on the device and nothing beyond them is read; outputs beyond them are 0.  A row whose
+    labels cannot be aligned (too few frames, a label equal to blank or outside [0, V)) gets log_prob -inf, start = end = 0,
+    duration 0 and log_confidence -inf.  Two calls give equal bits.  Limits: 1 <= T <= 4096, 2 <= V <= 128, L <= 2047."""
+    given = [t for t in (logits, lengths, labels, label_lengths) if t is not None]
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in given) or logits is None or labels is None:
+        raise RuntimeError("ctc_segment: GPU tensors only")
+    if logits.dim() != 3 or labels.dim() != 2 or labels.shape[0] != logits.shape[0]:
+        raise RuntimeError(f"ctc_segment: logits [B, T, V] and labels [B, L] with the same B, got {list(logits.shape)} and "
+                           f"{list(labels.shape)}")
+    dev = logits.device
+    logits = logits.contiguous().float()
+    B, T, V = logits.shape
+    blank = int(blank)
+    labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+    il = lengths.to(device=dev, dtype=torch.int32).contiguous() if lengths is not None else None
+    ll = label_lengths.to(device=dev, dtype=torch.int32).contiguous() if label_lengths is not None else None
+    if (il is not None and il.numel() != B) or (ll is not None and ll.numel() != B):
+        raise RuntimeError(f"ctc_segment: lengths and label_lengths must have {B} elements")
+    width = labels.shape[1]
+    if width == 0:                                       # no column: every row is empty
+        labels, ll = labels.new_zeros((B, 1)), torch.zeros((B,), dtype=torch.int32, device=dev)
+    Lmax = labels.shape[1]
+    nbytes = N.helper("v100_ctc_segment_workspace_bytes", B, T, Lmax) if B >= 1 else -1
+    if nbytes <= 0 or not 2 <= V <= 128 or not 0 <= blank < V:
+        raise RuntimeError(f"ctc_segment: unsupported shape or argument (B = {B} >= 1, 1 <= T = {T} <= 4096, 2 <= V = {V} <= 128, "
+                           f"L = {width} <= 2047 and 0 <= blank = {blank} < V are the limits)")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)    # noqa: E731
+    log_prob, start, end, duration, log_conf = f32(B), i32(B, Lmax), i32(B, Lmax), f32(B, Lmax), f32(B, Lmax)
+    NW = (Lmax + 1) // 2
+    word = (i32(B, NW), i32(B, NW), i32(B, NW), i32(B, NW), f32(B, NW), i32(B)) if sep is not None else (None,) * 6
+    N.call("v100_ctc_segment", logits, il, labels, ll, ws, log_prob, start, end, duration, log_conf, *word, B, T, V, Lmax, blank,
+           0 if sep is None else int(sep))
+    if width == 0:
+        start, end, duration, log_conf = (t[:, :0] for t in (start, end, duration, log_conf))
+        word = tuple(t[:, :0] for t in word[:5]) + (word[5],) if sep is not None else word
+    return CTCSegments(log_prob, start, end, duration, log_conf, *word)

@@ -217,10 +217,11 @@ class ASRPipeline:
     and their frame counts then come from one ragged launch, mel.transform(wav, lengths)), frames per row when it has none
     (wav_or_mel is the padded feature batch); the decode stops at model.output_length(frames) of each row."""
 
-    def __init__(self, model, mel=None, beam_size=None, nbest=1, lm=None, lm_weight=0.5, length_bonus=0.0):
+    def __init__(self, model, mel=None, beam_size=None, nbest=1, lm=None, lm_weight=0.5, length_bonus=0.0, frame_seconds=None):
         if lm is not None and beam_size is None:
             raise RuntimeError("ASRPipeline: a language model needs a beam_size (the greedy decode has nothing to rank)")
         self.model, self.mel = model, mel
+        self.frame_seconds = frame_seconds                     # seconds per output frame (segments, transcribe_timed); None: from the mel
         self.beam_size, self.nbest_size = beam_size, nbest     # beam_size=None: the greedy decode
         self.lm, self.lm_weight, self.length_bonus = lm, lm_weight, length_bonus
 
@@ -246,8 +247,12 @@ class ASRPipeline:
     def __call__(self, wav_or_mel: torch.Tensor, lengths=None):
         """(ids [B, T'] int64 zero padded, lens [B] int32): the greedy decode, or with a beam_size the best hypothesis of the prefix
         beam search (decode.ctc_beam_search, K24)."""
-        from .decode import ctc_greedy_decode
         logits, out_len = self._logits(wav_or_mel, lengths)
+        return self._best(logits, out_len)
+
+    def _best(self, logits, out_len):
+        """The decode of __call__ on logits that are already there."""
+        from .decode import ctc_greedy_decode
         if self.beam_size is None:
             return ctc_greedy_decode(logits) if out_len is None else ctc_greedy_decode(logits, out_len)
         ids, n = self._beam(logits, out_len, 1)[:2]
@@ -273,6 +278,59 @@ class ASRPipeline:
         ids, n = self(wave, wave_len)
         ids, n = ids.cpu(), n.cpu()
         return [decode(ids[i, :int(n[i])]) for i in range(ids.shape[0])]
+
+    def _frame_seconds(self, who: str) -> float:
+        """Seconds per output frame: the constructor's frame_seconds, else the mel's hop times the model's frame reduction."""
+        if self.frame_seconds is not None:
+            return float(self.frame_seconds)
+        if self.mel is None:
+            raise RuntimeError(f"ASRPipeline.{who}: the pipeline has no mel transform to take the frame period from "
+                               "(pass frame_seconds= to the constructor)")
+        frames = int(self.model.output_length(torch.tensor([4096])))
+        return self.mel.hop_length / self.mel.sample_rate * 4096 / frames
+
+    @torch.no_grad()
+    def segments(self, wav_or_mel: torch.Tensor, lengths=None, sep=1):
+        """One forward, the decode of __call__ (greedy, beam, or beam with the LM, as configured), then decode.ctc_segment (K26) of that
+        hypothesis on the same logits.  Returns a dict of device tensors: "ids" [B, T'] int64 and "ids_len" [B] as __call__ returns
+        them, the fields of decode.CTCSegments ("log_prob" [B]; "start", "end", "duration", "log_confidence" [B, L], L = the longest
+        hypothesis; "word_first", "word_count", "word_start", "word_end", "word_log_confidence" [B, (L + 1) // 2] and "n_words" [B],
+        None with sep=None) in output frames, and "frame_seconds" (a float: multiply a frame index by it).  One read-back, of
+        ids_len.max(), sizes L.  The numbers are posteriors of the alignment GIVEN the hypothesis, not of the hypothesis being right."""
+        from .decode import ctc_segment
+        frame_seconds = self._frame_seconds("segments")
+        logits, out_len = self._logits(wav_or_mel, lengths)
+        ids, n = self._best(logits, out_len)
+        L = max(int(n.max()), 1)                               # the one read-back: the label tensors are exactly that wide
+        seg = ctc_segment(logits, out_len, ids[:, :L], n, sep=sep)
+        out = {"ids": ids, "ids_len": n}
+        out.update(seg._asdict())
+        out["frame_seconds"] = frame_seconds
+        return out
+
+    def transcribe_timed(self, paths, decode: Callable[[torch.Tensor], str], sep=1):
+        """WAV files -> one entry per file: {"text", "log_prob", "words"}, words a list of {"word", "start", "end", "confidence"} with
+        times in seconds and confidence = exp(word_log_confidence); audio_io.load_batch, segments, then `decode` (the caller's
+        tokenizer.decode, ids tensor -> str) on each row's ids and on each word's; one device-to-host copy per tensor.  A time is a
+        frame index times frame_seconds; the last frame reaches past the last sample (the mel frames are centred), so an end is cut
+        at the file's own duration.  Needs a `mel`."""
+        from .audio_io import load_batch
+        if self.mel is None:
+            raise RuntimeError("ASRPipeline.transcribe_timed: the pipeline has no mel transform to turn waveforms into features")
+        if sep is None:
+            raise RuntimeError("ASRPipeline.transcribe_timed: words need a separator id (segments(sep=None) gives the label level)")
+        wave, wave_len = load_batch(paths, self.mel.sample_rate, self.mel.dft_basis.device)
+        out = self.segments(wave, wave_len, sep)
+        fs = out["frame_seconds"]
+        keys = ("ids", "ids_len", "log_prob", "word_first", "word_count", "word_start", "word_end", "word_log_confidence", "n_words")
+        ids, n, log_prob, first, count, start, end, conf, nw = (out[k].cpu() for k in keys)
+        conf, seconds = torch.exp(conf), wave_len.cpu().double() / self.mel.sample_rate
+        result = []
+        for i in range(ids.shape[0]):
+            words = [{"word": decode(ids[i, int(first[i, w]):int(first[i, w]) + int(count[i, w])]), "start": int(start[i, w]) * fs,
+                      "end": min(int(end[i, w]) * fs, float(seconds[i])), "confidence": float(conf[i, w])} for w in range(int(nw[i]))]
+            result.append({"text": decode(ids[i, :int(n[i])]), "log_prob": float(log_prob[i]), "words": words})
+        return result
 
 
     @torch.no_grad()
