@@ -463,8 +463,16 @@ long long v100_ir_prep_bytes(const int* shape);
 long long v100_ir_fwd_workspace_bytes(const int* shape);
 /* eval mode (inference): folded BatchNorm coefficients + bf16 weight copies in a caller-owned cache (refill with
  * v100_ir_eval_prep whenever a parameter or running statistic changes), then 3 launches per block and call.
- *  prep ptrs: w1 | g1 b1 rm1 rv1 | g2 b2 rm2 rv2 | w3 | g3 b3 rm3 rv3 | cache   (15)
- *  fwd  ptrs: x | w1 wd w3 | cache | h1 [B,hid,T] h2 [B,hid,T'] y [B,Cout,T']   (8) */
+ * Pointer tables (HOST arrays of device pointers):
+ *  prep: w1 | g1 b1 rm1 rv1 | g2 b2 rm2 rv2 | w3 | g3 b3 rm3 rv3 | cache   (15; cache = v100_ir_eval_cache_bytes(shape) bytes)
+ *  fwd:  x | w1 wd w3 | cache | h1 h2 y                                    (8)
+ * The eval entry points read the nine leading ints of `shape` (v100_ir_eval_cache_bytes may be given no more), ignore the flags, and
+ * read shape[10] NOT as the training act16 level but as the layout of the forward's tensors (v100_ir_eval_prep does not read it):
+ *  0  x [B,Cin,T], h1 [B,hid,T], h2 [B,hid,T'], y [B,Cout,T'], all fp32; any operand format
+ *  1  h1 / h2 bf16 [B][hid][v100_row_pitch16(T, B)], x and y as at 0; bf16 operands and a shape with v100_ir_act16_supported
+ *  2  channel-major: x [Cin][B P] fp32, h1 / h2 [hid][B P] in the 16-bit operand format (bf16, or fp16 at bf16 = 2), y [Cout][B P]
+ *     fp32, P = v100_row_pitch16(T, B); stride 1, T <= 768, B P <= 0x7fffff00, and a shape whose bf16 twin has v100_ir_act16_supported
+ * (any other non-zero value is taken as 1).  A combination outside these rules returns 1 (bad shape). */
 long long v100_ir_eval_cache_bytes(const int* shape);
 int v100_ir_eval_prep(const int* shape, const void* const* ptrs, void* stream);
 int v100_ir_fwd_eval(const int* shape, const void* const* ptrs, void* stream);

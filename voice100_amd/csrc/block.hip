@@ -2,8 +2,8 @@
 // (training mode) or backward on the given stream, or (the stack executor, at the end of the file) of a run of consecutive blocks:
 // ~12 (forward) / ~20 (backward) Python->C crossings per block become one.  Host code only, no kernel: it sequences the kernel entry
 // points of this library (no allocation: the caller passes the outputs, the tensors saved for backward and ONE workspace blob that
-// is carved here).  v100_ir_fwd_train / v100_ir_bwd only unpack their shape array (block_shape.h) and pointer table into IrShape and
-// IrFwdArgs / IrBwdArgs; ir_fwd_train / ir_bwd sequence the launches, and the stack executor calls those two with structs of its own.
+// is carved here).  The extern "C" entry points only unpack their shape array (block_shape.h) and pointer table into IrShape and an
+// argument struct; ir_fwd_train / ir_bwd / ir_eval_prep / ir_fwd_eval sequence the launches, and the stack executors call those themselves.
 #include "common.h"
 #include "../../include/voice100_hip.h"
 #include "depthwise_common.h"   // DwFin / DwPre: BatchNorm finalisation inside the producing / the consuming kernel
@@ -13,7 +13,6 @@
 // GEMM's slab, backward BatchNorm-2 backward from the project backward-data GEMM's slab): bit-identical results, 16 launches fewer,
 // 3.30 -> 3.24 ms/step although the depthwise kernels themselves get slower (A/B on one box: profiles/r06_dw_ab.txt).
 
-static inline int conv_out(int t, int k, int s) { return (t + 2 * ((k - 1) / 2) - k) / s + 1; }
 static inline size_t al256(size_t v) { return (v + 255) & ~size_t(255); }
 static const float kMom = 0.1f, kEps = 1e-5f;
 #define CK(call) do { rc = (call); if (rc) return rc; } while (0)
@@ -339,94 +338,90 @@ extern "C" int v100_ir_bwd(const int* sh, const void* const* P, void* stream) {
 
 // ---- eval mode: BatchNorm folded to per-channel scale/shift inside three kernels (pw+BN+ReLU6, dw+BN+ReLU6, pw+BN(+x)).
 // The folded coefficients and the bf16 weight copies only change when the parameters do, so they live in a caller-owned
-// cache filled by v100_ir_eval_prep; a forward is then 3 launches from one call.
+// cache filled by v100_ir_eval_prep; a forward is then 3 launches from one call.  (shape[IR_ACT16] here: IrEvalLayout, block_shape.h)
 struct IrEvalCache { void *w1bf, *w3bf; float *s1, *t1, *s2, *t2, *s3, *t3; };
-static size_t ir_eval_carve(const int* sh, void* base, IrEvalCache& w) {
-    const int cin = sh[IR_CIN], hid = sh[IR_HID], cout = sh[IR_COUT];
+static size_t ir_eval_carve(const IrShape& s, void* base, IrEvalCache& w) {
     Carver c(base);
     w.w1bf = w.w3bf = nullptr;
-    if (sh[IR_BF16]) { w.w1bf = c.take<u16>((size_t)hid * cin); w.w3bf = c.take<u16>((size_t)cout * hid); }
-    w.s1 = c.take<float>(hid); w.t1 = c.take<float>(hid); w.s2 = c.take<float>(hid); w.t2 = c.take<float>(hid);
-    w.s3 = c.take<float>(cout); w.t3 = c.take<float>(cout);
+    if (s.bf) { w.w1bf = c.take<u16>((size_t)s.hid * s.cin); w.w3bf = c.take<u16>((size_t)s.cout * s.hid); }
+    w.s1 = c.take<float>(s.hid); w.t1 = c.take<float>(s.hid); w.s2 = c.take<float>(s.hid); w.t2 = c.take<float>(s.hid);
+    w.s3 = c.take<float>(s.cout); w.t3 = c.take<float>(s.cout);
     return c.used + 256;
 }
-extern "C" long long v100_ir_eval_cache_bytes(const int* shape) {
-    IrEvalCache w;
-    return (long long)ir_eval_carve(shape, nullptr, w);
+extern "C" long long v100_ir_eval_cache_bytes(const int* shape) { IrEvalCache w; return (long long)ir_eval_carve(ir_shape(shape, false), nullptr, w); }
+// v100_ir_eval_prep's table (15): w1 | g1 b1 rm1 rv1 | g2 b2 rm2 rv2 | w3 | g3 b3 rm3 rv3 | cache
+struct IrEvalBn { const float *gamma, *beta, *rm, *rv; };
+struct IrEvalParams { const float* w1; IrEvalBn bn1, bn2; const float* w3; IrEvalBn bn3; };
+static IrEvalParams ir_eval_params(const void* const* t) {
+    auto bn = [&](int j) { return IrEvalBn{(const float*)t[j], (const float*)t[j + 1], (const float*)t[j + 2], (const float*)t[j + 3]}; };
+    return {(const float*)t[0], bn(1), bn(5), (const float*)t[9], bn(10)};
 }
-// ptrs: 0 w1 | 1 g1 2 b1 3 rm1 4 rv1 | 5 g2 6 b2 7 rm2 8 rv2 | 9 w3 | 10 g3 11 b3 12 rm3 13 rv3 | 14 cache
-extern "C" int v100_ir_eval_prep(const int* sh, const void* const* P, void* stream) {
-    if (!sh || !P) return V100_ERR_NULL;
-    const int cin = sh[IR_CIN], hid = sh[IR_HID], cout = sh[IR_COUT];
-    IrEvalCache c;
-    ir_eval_carve(sh, const_cast<void*>(P[14]), c);
+// v100_ir_fwd_eval's table (8): x | w1 wd w3 | cache | h1 [B,hid,T] h2 [B,hid,T2] y [B,cout,T2] (the 16-bit layouts of h1 / h2: ir_fwd_eval)
+struct IrEvalArgs { const float *x, *w1, *wd, *w3; void* cache; float *h1, *h2, *y; };
+static IrEvalArgs ir_eval_args(const void* const* t) {
+    return {(const float*)t[0], (const float*)t[1], (const float*)t[2], (const float*)t[3], const_cast<void*>(t[4]), (float*)t[5], (float*)t[6], (float*)t[7]};
+}
+static int ir_eval_prep(const IrShape& s, const IrEvalParams& p, void* cache, hipStream_t stream) {
+    IrEvalCache c; ir_eval_carve(s, cache, c);
     int rc;
-    if (sh[IR_BF16] == 2) {                                   // fp16 operands
-        CK(v100_weight_prep_f16((const float*)P[0], hid, cin, c.w1bf, stream));
-        CK(v100_weight_prep_f16((const float*)P[9], cout, hid, c.w3bf, stream));
-    } else if (sh[IR_BF16]) {
-        CK(v100_weight_prep((const float*)P[0], hid, cin, c.w1bf, nullptr, nullptr, stream));
-        CK(v100_weight_prep((const float*)P[9], cout, hid, c.w3bf, nullptr, nullptr, stream));
+    if (s.bf == 2) {                                   // fp16 operands
+        CK(v100_weight_prep_f16(p.w1, s.hid, s.cin, c.w1bf, stream));
+        CK(v100_weight_prep_f16(p.w3, s.cout, s.hid, c.w3bf, stream));
+    } else if (s.bf) {
+        CK(v100_weight_prep(p.w1, s.hid, s.cin, c.w1bf, nullptr, nullptr, stream));
+        CK(v100_weight_prep(p.w3, s.cout, s.hid, c.w3bf, nullptr, nullptr, stream));
     }
-    CK(v100_bn_eval_coeffs((const float*)P[1], (const float*)P[2], (const float*)P[3], (const float*)P[4], kEps, c.s1, c.t1, hid, stream));
-    CK(v100_bn_eval_coeffs((const float*)P[5], (const float*)P[6], (const float*)P[7], (const float*)P[8], kEps, c.s2, c.t2, hid, stream));
-    CK(v100_bn_eval_coeffs((const float*)P[10], (const float*)P[11], (const float*)P[12], (const float*)P[13], kEps, c.s3, c.t3, cout, stream));
+    CK(v100_bn_eval_coeffs(p.bn1.gamma, p.bn1.beta, p.bn1.rm, p.bn1.rv, kEps, c.s1, c.t1, s.hid, stream));
+    CK(v100_bn_eval_coeffs(p.bn2.gamma, p.bn2.beta, p.bn2.rm, p.bn2.rv, kEps, c.s2, c.t2, s.hid, stream));
+    CK(v100_bn_eval_coeffs(p.bn3.gamma, p.bn3.beta, p.bn3.rm, p.bn3.rv, kEps, c.s3, c.t3, s.cout, stream));
     return V100_OK;
 }
-// ptrs: 0 x | 1 w1 2 wd 3 w3 | 4 cache | 5 h1 [B,hid,T] 6 h2 [B,hid,T2] 7 y [B,cout,T2]
-extern "C" int v100_ir_fwd_eval(const int* sh, const void* const* P, void* stream) {
+extern "C" int v100_ir_eval_prep(const int* sh, const void* const* P, void* stream) {
     if (!sh || !P) return V100_ERR_NULL;
-    const int B = sh[IR_B], cin = sh[IR_CIN], hid = sh[IR_HID], cout = sh[IR_COUT], T = sh[IR_T], K = sh[IR_K], S = sh[IR_STRIDE];
-    const int res = sh[IR_RES], bf = sh[IR_BF16];
-    const int pad = (K - 1) / 2, T2 = conv_out(T, K, S);
-    const float* x = (const float*)P[0];
-    IrEvalCache c;
-    ir_eval_carve(sh, const_cast<void*>(P[4]), c);
-    float *h1 = (float*)P[5], *h2 = (float*)P[6], *y = (float*)P[7];
+    return ir_eval_prep(ir_shape(sh, false), ir_eval_params(P), const_cast<void*>(P[14]), (hipStream_t)stream);
+}
+static int ir_fwd_eval(const IrShape& s, IrEvalLayout layout, const IrEvalArgs& a, hipStream_t stream) {
+    const int B = s.B, cin = s.cin, hid = s.hid, cout = s.cout, T = s.T, K = s.K, S = s.S, bf = s.bf, T2 = s.T2;
+    const float *x = a.x, *r = s.res ? a.x : nullptr;
+    IrEvalCache c; ir_eval_carve(s, a.cache, c);
     int rc;
-    if (sh[IR_ACT16] == 2) {
-        // CHANNEL-MAJOR inference (round 4): x [cin][B P] fp32, h1 / h2 [hid][B P] 16-bit, y [cout][B P] fp32, P = pitch16(T) -- every
+    if (layout != IR_EVAL_F32) {
+        // 16-BIT ROWS (precision "bf16"): the two hidden tensors (each 4x the block's width, already BatchNorm'ed and clamped to [0, 6])
+        // are stored as bf16 [B][hid][pitch16(T)] -- half the bytes of the three kernels' big streams; the GEMMs round them to bf16 as
+        // operands anyway.  Same three launches.
+        // CHANNEL-MAJOR (round 4): x [cin][B P] fp32, h1 / h2 [hid][B P] 16-bit, y [cout][B P] fp32, P = pitch16(T) -- every
         // utterance of the batch back to back in ONE [C x (B P)] matrix.  The two 1x1 convolutions are then ONE GEMM over all B P columns
         // (1-second chunks, T' = 51: 128-column tiles are full instead of 40 % full), a channel's rows are contiguous for the depthwise
         // kernel (the order it walks them in), short rows are packed several to a wave item.  The columns T .. P-1 of an utterance are
         // padding: finite garbage that no valid column ever reads (GEMM columns are independent; the depthwise kernel masks them).
-        // Hidden tensors in the GEMMs' operand format: bf16, or fp16 at precision "fp16".
-        int shb[IR_NSHAPE];
-        for (int i = 0; i < IR_NSHAPE; ++i) shb[i] = sh[i];
-        shb[IR_BF16] = 1;
-        if ((bf != 1 && bf != 2) || S != 1 || T > 768 || !v100_ir_act16_supported(shb)) return V100_ERR_SHAPE;
+        // Hidden tensors in the GEMMs' operand format: bf16, or fp16 at precision "fp16" (held to the shape rules of its bf16 twin).
+        const bool cm = layout == IR_EVAL_CM;
+        IrShape twin = s; twin.bf = 1;
+        if ((cm ? (bf != 1 && bf != 2) || S != 1 || T > 768 : bf != 1) || !ir_act16_supported(twin)) return V100_ERR_SHAPE;
         const long long N = (long long)B * pitch16(T, B);
-        if (N > 0x7fffff00LL) return V100_ERR_SHAPE;
-        const int f16 = bf == 2 ? PW_IO_F16 : 0;
-        CK(v100_pw_gemm_io(c.w1bf, x, nullptr, nullptr, nullptr, nullptr, 0, h1, c.s1, c.t1, nullptr, 2, nullptr, 1, hid, cin, (int)N, PW_IO_Y | f16, stream));
-        CK(dw_fwd_eval_io(h1, (const float*)P[2], c.s2, c.t2, h2, B, hid, T, K, stream, 1, bf == 2));
-        CK(v100_pw_gemm_io(c.w3bf, h2, nullptr, nullptr, nullptr, nullptr, 0, y, c.s3, c.t3, res ? x : nullptr, 3, nullptr, 1, cout, hid, (int)N, PW_IO_X | f16, stream));
+        if (cm && N > 0x7fffff00LL) return V100_ERR_SHAPE;
+        const int nb = cm ? 1 : B, n1 = cm ? (int)N : T, n2 = cm ? (int)N : T2, f16 = bf == 2 ? PW_IO_F16 : 0;     // (rows: bf == 1)
+        CK(v100_pw_gemm_io(c.w1bf, x, nullptr, nullptr, nullptr, nullptr, 0, a.h1, c.s1, c.t1, nullptr, 2, nullptr, nb, hid, cin, n1, PW_IO_Y | f16, stream));
+        CK(dw_fwd_eval_io(a.h1, a.wd, c.s2, c.t2, a.h2, B, hid, T, K, stream, cm, bf == 2));
+        CK(v100_pw_gemm_io(c.w3bf, a.h2, nullptr, nullptr, nullptr, nullptr, 0, a.y, c.s3, c.t3, r, 3, nullptr, nb, cout, hid, n2, PW_IO_X | f16, stream));
         return V100_OK;
     }
-    if (sh[IR_ACT16]) {
-        // inference at precision "bf16": the two hidden tensors (each 4x the block's width, already BatchNorm'ed and clamped to [0, 6])
-        // are stored as bf16 [B][hid][pitch16(T)] -- half the bytes of the three kernels' big streams; the GEMMs round them to bf16 as
-        // operands anyway.  Same three launches.
-        if (bf != 1 || !v100_ir_act16_supported(sh)) return V100_ERR_SHAPE;
-        CK(v100_pw_gemm_io(c.w1bf, x, nullptr, nullptr, nullptr, nullptr, 0, h1, c.s1, c.t1, nullptr, 2, nullptr, B, hid, cin, T, PW_IO_Y, stream));
-        CK(dw_fwd_eval_io(h1, (const float*)P[2], c.s2, c.t2, h2, B, hid, T, K, stream));
-        CK(v100_pw_gemm_io(c.w3bf, h2, nullptr, nullptr, nullptr, nullptr, 0, y, c.s3, c.t3, res ? x : nullptr, 3, nullptr, B, cout, hid, T2, PW_IO_X, stream));
-        return V100_OK;
-    }
-    CK(v100_pw_gemm((const float*)P[1], c.w1bf, x, nullptr, nullptr, nullptr, nullptr, 0, h1, nullptr, c.s1, c.t1, nullptr, 2, nullptr, B, hid, cin, T, bf, stream));
-    CK(v100_dwconv(h1, nullptr, (const float*)P[2], nullptr, nullptr, nullptr, 0, h2, nullptr, c.s2, c.t2, 1, nullptr, v100_dw_num_groups(B, hid),
-                   B, hid, T, T2, K, S, pad, 0, 1, 0, stream));
-    CK(v100_pw_gemm((const float*)P[3], c.w3bf, h2, nullptr, nullptr, nullptr, nullptr, 0, y, nullptr, c.s3, c.t3, res ? x : nullptr, 3, nullptr, B, cout, hid, T2, bf, stream));
+    CK(v100_pw_gemm(a.w1, c.w1bf, x, nullptr, nullptr, nullptr, nullptr, 0, a.h1, nullptr, c.s1, c.t1, nullptr, 2, nullptr, B, hid, cin, T, bf, stream));
+    CK(v100_dwconv(a.h1, nullptr, a.wd, nullptr, nullptr, nullptr, 0, a.h2, nullptr, c.s2, c.t2, 1, nullptr, v100_dw_num_groups(B, hid),
+                   B, hid, T, T2, K, S, s.pad, 0, 1, 0, stream));
+    CK(v100_pw_gemm(a.w3, c.w3bf, a.h2, nullptr, nullptr, nullptr, nullptr, 0, a.y, nullptr, c.s3, c.t3, r, 3, nullptr, B, cout, hid, T2, bf, stream));
     return V100_OK;
 }
-
+extern "C" int v100_ir_fwd_eval(const int* sh, const void* const* P, void* stream) {
+    if (!sh || !P) return V100_ERR_NULL;
+    return ir_fwd_eval(ir_shape(sh, false), ir_eval_layout(sh), ir_eval_args(P), (hipStream_t)stream);
+}
 extern "C" int v100_ir_stack_fwd_eval(int n, const int* shapes, const void* const* ptrs, void* stream) {
     if (!shapes || !ptrs) return V100_ERR_NULL;
     if (n < 0) return V100_ERR_SHAPE;
-    for (int i = 0; i < n; ++i) {
-        const int rc = v100_ir_fwd_eval(shapes + (size_t)i * IR_NSHAPE, ptrs + (size_t)i * 8, stream);
-        if (rc != V100_OK) return rc;
-    }
+    int rc;
+    for (int i = 0; i < n; ++i, shapes += IR_NSHAPE, ptrs += 8)
+        CK(ir_fwd_eval(ir_shape(shapes, false), ir_eval_layout(shapes), ir_eval_args(ptrs), (hipStream_t)stream));
     return V100_OK;
 }
 

@@ -13,6 +13,10 @@ enum { IR_B, IR_CIN, IR_HID, IR_COUT, IR_T, IR_K, IR_STRIDE, IR_RES, IR_BF16, IR
 // flag bits of shape[IR_PREPPED] that only the stack executor sets (the public three: V100_IR_*, voice100_hip.h)
 enum { IR_F_NO_Y32 = 4, IR_F_DY16 = 16, IR_F_DX16 = 32, IR_F_DEFER = 64 };
 
+// The EVAL entry points (v100_ir_eval_prep / v100_ir_fwd_eval / v100_ir_stack_fwd_eval) parse the nine leading ints only (IrShape::act16, the training
+// level, stays 0) and read shape[IR_ACT16] as the storage of the two hidden tensors: fp32 rows, bf16 [B][hid][pitch16(T)] rows, or channel-major
+enum IrEvalLayout { IR_EVAL_F32 = 0, IR_EVAL_ROWS16 = 1, IR_EVAL_CM = 2 };
+inline IrEvalLayout ir_eval_layout(const int* sh) { return sh[IR_ACT16] == IR_EVAL_CM ? IR_EVAL_CM : sh[IR_ACT16] ? IR_EVAL_ROWS16 : IR_EVAL_F32; }
 // A shape array parsed once.  ir_shape and ir_shape_ints are the only code that knows the flag bits.
 struct IrShape {
     int B, cin, hid, cout, T, K, S, res, bf;     // bf: operand format, 0 fp32 / 1 bf16 (/ 2 fp16: inference only)

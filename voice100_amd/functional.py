@@ -188,25 +188,6 @@ def _pw_gemm(a_f32, a_bf, x, y, m, k, t, b, bf16, x2=None, xa=None, xb=None, xc=
     N.call("v100_pw_gemm", a_f32, a_bf, x, x2, xa, xb, xc, x_mode, y, bias, ea, eb, r, epi, stats, b, m, k, t, int(bf16))
 
 
-def _bn_train(stats, parts, count, bn_w, bn_b, rm, rv, nbt, c, like):
-    scale, shift, mean, rstd = (_f32(c, like=like) for _ in range(4))
-    N.call("v100_bn_finalize_train", stats, parts, count, bn_w, bn_b, rm, rv, nbt, BN_MOMENTUM, BN_EPS, scale, shift, mean, rstd, c)
-    _touched((rm, rv, nbt))
-    return scale, shift, mean, rstd
-
-
-def _bn_eval(bn_w, bn_b, rm, rv, c, like):
-    scale, shift = _f32(c, like=like), _f32(c, like=like)
-    N.call("v100_bn_eval_coeffs", bn_w, bn_b, rm, rv, BN_EPS, scale, shift, c)
-    return scale, shift
-
-
-def _bn_bwd(partial, parts, count, gamma, mean, rstd, c, like):
-    p, q, r, dg, db = (_f32(c, like=like) for _ in range(5))
-    N.call("v100_bn_bwd_finalize", partial, parts, count, gamma, mean, rstd, p, q, r, dg, db, c)
-    return p, q, r, dg, db
-
-
 def _ptr_table(items):
     arr = (ctypes.c_void_p * len(items))()
     for i, t in enumerate(items):
@@ -216,6 +197,10 @@ def _ptr_table(items):
 
 # The block executor's shape array (include/voice100_hip.h): where its flags and act16 level sit, and the three public flag bits
 _SH_FLAGS, _SH_ACT16 = 9, 10
+# The eval entry points read shape[_SH_ACT16] as the storage of the two hidden tensors instead: 0 = fp32 rows, 16-bit pitched rows, channel-major
+_EVAL_ROWS16, _EVAL_CM = 1, 2
+# the eight slots of a block in v100_ir_fwd_eval's / v100_ir_stack_fwd_eval's pointer table
+_EV_X, _EV_W1, _EV_WD, _EV_W3, _EV_CACHE, _EV_H1, _EV_H2, _EV_Y = range(8)
 _IR_PREPPED, _IR_SHADOW_SLOTS, _IR_FROZEN = 1, 2, 8
 # Of a block's 18 parameter / buffer slots (_block_tensors), the nine trainable ones -- w1 g1 b1 wd g2 b2 w3 g3 b3: the order of the
 # executors' gradients -- and the nine running-statistics buffers
@@ -597,41 +582,59 @@ def prepared_weights_of(blk, precision: Optional[str] = None):
     return None
 
 
+def _eval_tensors(bt):
+    """Of a block's 18 tensors (_block_tensors): (the 14 of v100_ir_eval_prep's table in its order -- w1 | g1 b1 rm1 rv1 | g2 b2 rm2 rv2 |
+    w3 | g3 b3 rm3 rv3 -- and then wd: everything an eval forward reads), w1, wd, w3.  The only statement of that order."""
+    return bt[0:5] + bt[7:11] + bt[12:17] + (bt[6],), bt[0], bt[6], bt[12]
+
+
+def _eval_shape(blk, w1, w3, B, cin, T, fmt, layout=0):
+    """(shape array, hid, cout) of an eval-mode block with these 1x1 weights on an input of width cin."""
+    hid, cout = w1.shape[0], w3.shape[0]
+    stride = 1 if layout == _EVAL_CM else int(blk.stride)            # (channel-major is stride 1 by definition)
+    shape = (ctypes.c_int * 11)(B, cin, hid, cout, T, int(blk.kernel_size), stride, int(bool(blk.use_residual)), int(fmt), 0, layout)
+    return shape, hid, cout
+
+
+def _eval_cache_fill(shape, tensors, device):
+    """A new eval cache (folded BatchNorm coefficients, 16-bit weight copies) of the block with these _eval_tensors."""
+    for t in tensors:
+        if not t.is_cuda or not t.is_contiguous():
+            raise RuntimeError("InvertedResidual: parameters and buffers must be contiguous CUDA tensors (no CPU fallback)")
+    cache = torch.empty(N.helper("v100_ir_eval_cache_bytes", shape), dtype=torch.uint8, device=device)
+    N.call("v100_ir_eval_prep", shape, _ptr_table(tensors[:14] + (cache,)))
+    return cache
+
+
+def _eval_cache_of(blk, shape, tensors, fmt, device):
+    """The cache kept on the module, refilled when the format or any tensor's storage or version has changed since it was filled."""
+    key = (fmt,) + tuple((t.data_ptr(), t._version) for t in tensors)
+    if getattr(blk, "_eval_key", None) != key:
+        blk._eval_cache, blk._eval_key = _eval_cache_fill(shape, tensors, device), key
+    return blk._eval_cache
+
+
 def inverted_residual_eval_cached(blk, x, precision: Optional[str] = None):
     """Eval-mode InvertedResidual through the block executor: the folded BatchNorm coefficients and bf16 weight copies
     are cached on the module (refilled when any parameter / running statistic changes: tensor versions are the key),
     so a forward is one host call = 3 kernel launches.  Inference only (no autograd)."""
     _check(x, "InvertedResidual")
     x = x.contiguous()
-    pw, dw, pl, bn3 = blk.conv[0], blk.conv[1], blk.conv[2], blk.conv[3]
-    bn1, bn2 = pw[1], dw[1]
-    w1, wd, w3 = pw[0].weight, dw[0].weight, pl.weight
+    tensors, w1, wd, w3 = _eval_tensors(_block_tensors(blk))
     bf16 = _fmt(precision)
     B, cin, T = x.shape
-    hid, cout, k = w1.shape[0], w3.shape[0], int(blk.kernel_size)
-    T2 = conv_out_len(T, k, blk.stride)
-    shape = (ctypes.c_int * 11)(B, cin, hid, cout, T, k, int(blk.stride), int(bool(blk.use_residual)), int(bf16), 0, 0)
-    params = (w1, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var,
-              w3, bn3.weight, bn3.bias, bn3.running_mean, bn3.running_var)
-    key = (bf16,) + tuple((t.data_ptr(), t._version) for t in params) + (wd.data_ptr(), wd._version)
-    if getattr(blk, "_eval_key", None) != key:
-        for t in params + (wd,):
-            if not t.is_cuda or not t.is_contiguous():
-                raise RuntimeError("InvertedResidual: parameters and buffers must be contiguous CUDA tensors (no CPU fallback)")
-        cache = torch.empty(N.helper("v100_ir_eval_cache_bytes", shape), dtype=torch.uint8, device=x.device)
-        N.call("v100_ir_eval_prep", shape, _ptr_table(tuple(t.detach() for t in params) + (cache,)))
-        blk._eval_cache, blk._eval_key = cache, key
+    shape, hid, cout = _eval_shape(blk, w1, w3, B, cin, T, bf16)
+    T2 = conv_out_len(T, int(blk.kernel_size), blk.stride)
+    cache = _eval_cache_of(blk, shape, tensors, bf16, x.device)
     y = _f32(B, cout, T2, like=x)
     if bf16 == 1 and _ACT16 and N.helper("v100_ir_act16_supported", shape):
         # precision "bf16": the two hidden tensors (4x the block's width, values in [0, 6] after BatchNorm + ReLU6) stored as bf16 with
         # pitched rows -- half the bytes of the big streams of all three kernels (the GEMMs round them to bf16 as operands anyway)
-        shape[_SH_ACT16] = 1
-        pitch = pitch16(T, B)
-        h1 = torch.empty((B, hid, pitch), dtype=torch.bfloat16, device=x.device)
-        h2 = torch.empty((B, hid, pitch), dtype=torch.bfloat16, device=x.device)
+        shape[_SH_ACT16] = _EVAL_ROWS16
+        h1, h2 = (torch.empty((B, hid, pitch16(T, B)), dtype=torch.bfloat16, device=x.device) for _ in range(2))
     else:
         h1, h2 = _f32(B, hid, T, like=x), _f32(B, hid, T2, like=x)
-    N.call("v100_ir_fwd_eval", shape, _ptr_table((x, w1.detach(), wd.detach(), w3.detach(), blk._eval_cache, h1, h2, y)))
+    N.call("v100_ir_fwd_eval", shape, _ptr_table((x, w1, wd, w3, cache, h1, h2, y)))
     return y
 
 
@@ -687,29 +690,17 @@ def cm_to_btc(x: torch.Tensor, B: int, T: int) -> torch.Tensor:
 def inverted_residual_eval_cm(blk, x: torch.Tensor, B: int, T: int, precision: Optional[str] = None) -> torch.Tensor:
     """Eval-mode InvertedResidual (stride 1) on a channel-major activation x [cin, B * P]: three launches (one GEMM over all
     columns, the depthwise stage, one GEMM), hidden tensors stored in the GEMMs' 16-bit operand format.  Inference only."""
-    pw, dw, pl, bn3 = blk.conv[0], blk.conv[1], blk.conv[2], blk.conv[3]
-    bn1, bn2 = pw[1], dw[1]
-    w1, wd, w3 = pw[0].weight, dw[0].weight, pl.weight
+    tensors, w1, wd, w3 = _eval_tensors(_block_tensors(blk))
     fmt = _fmt(precision)
-    hid, cin, cout, k = w1.shape[0], w1.shape[1], w3.shape[0], int(blk.kernel_size)
+    cin = w1.shape[1]
     P = pitch16(T, B)
     if x.shape != (cin, B * P):
         raise RuntimeError("inverted_residual_eval_cm: x must be [cin, B * pitch(T)]")
-    shape = (ctypes.c_int * 11)(B, cin, hid, cout, T, k, 1, int(bool(blk.use_residual)), int(fmt), 0, 0)
-    params = (w1, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var,
-              w3, bn3.weight, bn3.bias, bn3.running_mean, bn3.running_var)
-    key = (fmt,) + tuple((t.data_ptr(), t._version) for t in params) + (wd.data_ptr(), wd._version)
-    if getattr(blk, "_eval_key", None) != key:
-        for t in params + (wd,):
-            if not t.is_cuda or not t.is_contiguous():
-                raise RuntimeError("InvertedResidual: parameters and buffers must be contiguous CUDA tensors (no CPU fallback)")
-        cache = torch.empty(N.helper("v100_ir_eval_cache_bytes", shape), dtype=torch.uint8, device=x.device)
-        N.call("v100_ir_eval_prep", shape, _ptr_table(tuple(t.detach() for t in params) + (cache,)))
-        blk._eval_cache, blk._eval_key = cache, key
-    shape[_SH_ACT16] = 2
+    shape, hid, cout = _eval_shape(blk, w1, w3, B, cin, T, fmt, _EVAL_CM)
+    cache = _eval_cache_of(blk, shape, tensors, fmt, x.device)
     h = torch.empty((2, hid, B * P), dtype=torch.float16 if fmt == 2 else torch.bfloat16, device=x.device)
     y = _f32(cout, B * P, like=x)
-    N.call("v100_ir_fwd_eval", shape, _ptr_table((x, w1.detach(), wd.detach(), w3.detach(), blk._eval_cache, h[0], h[1], y)))
+    N.call("v100_ir_fwd_eval", shape, _ptr_table((x, w1, wd, w3, cache, h[0], h[1], y)))
     return y
 
 
@@ -744,23 +735,16 @@ def ir_stack_eval_cm(blocks, x: torch.Tensor, B: int, T: int, precision: Optiona
         plan.hid_max = plan.cout_max = 0
         cin_prev = x.shape[0]
         for i, (blk, bt) in enumerate(zip(blocks, tens)):
-            (w1, g1, b1, rm1, rv1, _n1, wd, g2, b2, rm2, rv2, _n2, w3, g3, b3, rm3, rv3, _n3) = bt
-            hid, cin, cout, k = w1.shape[0], w1.shape[1], w3.shape[0], int(blk.kernel_size)
+            tensors, w1, wd, w3 = _eval_tensors(bt)
+            cin = w1.shape[1]
             if cin != cin_prev or int(blk.stride) != 1:
                 raise RuntimeError("ir_stack_eval_cm: blocks must chain (cin == previous cout) at stride 1")
+            shape, hid, cout = _eval_shape(blk, w1, w3, B, cin, T, fmt, _EVAL_CM)
             cin_prev = cout
-            params = (w1, g1, b1, rm1, rv1, g2, b2, rm2, rv2, w3, g3, b3, rm3, rv3)
-            for t in params + (wd,):
-                if not t.is_cuda or not t.is_contiguous():
-                    raise RuntimeError("InvertedResidual: parameters and buffers must be contiguous CUDA tensors (no CPU fallback)")
-            shape = (ctypes.c_int * 11)(B, cin, hid, cout, T, k, 1, int(bool(blk.use_residual)), int(fmt), 0, 0)
-            cache = torch.empty(N.helper("v100_ir_eval_cache_bytes", shape), dtype=torch.uint8, device=x.device)
-            N.call("v100_ir_eval_prep", shape, _ptr_table(tuple(t.detach() for t in params) + (cache,)))
-            shape[_SH_ACT16] = 2
-            for j in range(11):
-                plan.shapes[11 * i + j] = shape[j]
-            plan.ptrs[8 * i + 1], plan.ptrs[8 * i + 2], plan.ptrs[8 * i + 3] = w1.data_ptr(), wd.data_ptr(), w3.data_ptr()
-            plan.ptrs[8 * i + 4] = cache.data_ptr()
+            cache = _eval_cache_fill(shape, tensors, x.device)
+            plan.shapes[11 * i:11 * i + 11] = shape[:]
+            for slot, t in ((_EV_W1, w1), (_EV_WD, wd), (_EV_W3, w3), (_EV_CACHE, cache)):
+                plan.ptrs[8 * i + slot] = t.data_ptr()
             plan.caches.append(cache)
             plan.keep.append(bt)        # every keyed tensor stays alive with the plan: id() of a replaced parameter can then never be reused by its successor
             plan.hid_max, plan.cout_max = max(plan.hid_max, hid), max(plan.cout_max, cout)
@@ -777,7 +761,7 @@ def ir_stack_eval_cm(blocks, x: torch.Tensor, B: int, T: int, precision: Optiona
     ptrs = plan.ptrs
     for i in range(n):
         y = out.data_ptr() if i == n - 1 else tmp[i & 1].data_ptr()
-        ptrs[8 * i], ptrs[8 * i + 5], ptrs[8 * i + 6], ptrs[8 * i + 7] = cur, h0, h1, y
+        ptrs[i * 8 + _EV_X], ptrs[i * 8 + _EV_H1], ptrs[i * 8 + _EV_H2], ptrs[i * 8 + _EV_Y] = cur, h0, h1, y
         cur = y
     N.call("v100_ir_stack_fwd_eval", n, plan.shapes, ptrs)
     return out
@@ -791,33 +775,6 @@ def pointwise_conv1d_cm(x: torch.Tensor, w: torch.Tensor, bias, precision: Optio
     W = _weights_of(w, cout, cin, fmt, False)
     y = _f32(cout, n, like=x)
     _pw_gemm(W.w, W.w_bf, x, y, cout, cin, n, 1, fmt, bias=bias.detach() if bias is not None else None, epi=0)
-    return y
-
-
-def inverted_residual_eval(x, w1, g1, b1, rm1, rv1, wd, g2, b2, rm2, rv2, w3, g3, b3, rm3, rv3,
-                           kernel_size, stride, use_residual, precision):
-    """Eval-mode InvertedResidual: BatchNorm folded to per-channel scale/shift inside the three kernels."""
-    _check(x, "InvertedResidual")
-    x = x.contiguous()
-    B, cin, T = x.shape
-    hid, cout = w1.shape[0], w3.shape[0]
-    k = int(kernel_size)
-    pad = (k - 1) // 2
-    T2 = conv_out_len(T, k, stride)
-    bf16 = _fmt(precision)
-    W1 = _Weights(w1.detach().reshape(hid, cin), bf16, False)
-    W3 = _Weights(w3.detach().reshape(cout, hid), bf16, False)
-    s1, t1 = _bn_eval(g1, b1, rm1, rv1, hid, x)
-    s2, t2 = _bn_eval(g2, b2, rm2, rv2, hid, x)
-    s3, t3 = _bn_eval(g3, b3, rm3, rv3, cout, x)
-    h1 = _f32(B, hid, T, like=x)
-    _pw_gemm(W1.w, W1.w_bf, x, h1, hid, cin, T, B, bf16, ea=s1, eb=t1, epi=2)
-    h2 = _f32(B, hid, T2, like=x)
-    G = N.helper("v100_dw_num_groups", B, hid)
-    N.call("v100_dwconv", h1, None, wd.detach().reshape(hid, k).contiguous(), None, None, None, 0, h2, None, s2, t2, 1, None, G,
-           B, hid, T, T2, k, stride, pad, 0, 1, 0)
-    y = _f32(B, cout, T2, like=x)
-    _pw_gemm(W3.w, W3.w_bf, h2, y, cout, hid, T2, B, bf16, ea=s3, eb=t3, r=x if use_residual else None, epi=3)
     return y
 
 
