@@ -596,6 +596,30 @@ int v100_ctc_segment(const float* logits, const int* in_len, const long long* la
                      int* start, int* end, float* duration, float* log_conf, int* word_first, int* word_count, int* word_start,
                      int* word_end, float* word_log_conf, int* n_words, int B, int T, int V, int Lmax, int blank, long long sep,
                      void* stream);
+/* K27, objective scores of synthesised WORLD features (csrc/dtw.hip): dynamic time warping between x [B][Tx][D] fp32 (the hypothesis)
+ * and y [B][Ty][D] fp32 (the reference), rows of x_len / y_len [B] int32 frames (NULL = full width; clamped to [0, width] on the
+ * device; nothing beyond a row's length is read), and the sums along the warping path.  With n, m the two lengths of a pair:
+ *   d(i,j) = sqrt(sum_{k = skip}^{D-1} (x[i][k] - y[j][k])^2)              (skip leading dimensions left out: MCD leaves out c0)
+ *   mode 0, DTW: C(0,0) = d(0,0), C(i,j) = d(i,j) + min(C(i-1,j-1), C(i-1,j), C(i,j-1)), predecessors outside the matrix absent, a
+ *     tie to the first candidate in that order; cost = C(n-1,m-1); the path is the backtrace from (n-1,m-1) to (0,0), reported
+ *     forwards, path_len in [max(n,m), n+m-1];
+ *   mode 1, identity: the path is (i,i) for i < min(n,m), cost the sum of d(i,i).
+ * f0x [B][Tx], f0y [B][Ty] fp32 in Hz, both or neither; a frame is voiced iff f0 >= f0_floor.  Over the path's pairs: voiced = both
+ * frames voiced, vuv_errors = exactly one voiced, f0_sq_cents = sum (1200 log2(f0x/f0y))^2 and f0_sq_hz = sum (f0x - f0y)^2 over the
+ * voiced pairs (all 0 without the f0 inputs).  A pair with n = 0 or m = 0 gives zeros everywhere.
+ * d is fp32 from differences with the root rounded once; the cumulative cost and the f0 sums are fp64.
+ * Outputs per row: cost, f0_sq_cents, f0_sq_hz [B] fp64; path_len, voiced, vuv_errors [B] int32; these six go together.  path
+ * [B][Tx+Ty-1][2] int32 (needs the six; zero beyond path_len) or NULL.  totals [6] fp64, into which the launches ADD the batch sums
+ * {pairs, cost, voiced, vuv_errors, f0_sq_cents, f0_sq_hz} (the caller zeroes it; the counts are sums of integers below 2^53 and
+ * stay exact).  The per-row outputs or totals may be NULL, not both.
+ * ws: v100_dtw_workspace_bytes(B, Tx, Ty, D, want_path) bytes (the distance matrices, 2-bit backpointers, and with want_path the
+ * reversed paths; -1 = unsupported shape).
+ * B >= 1, 1 <= Tx, Ty <= 4096, 0 <= skip < D, D - skip <= 64, mode 0 or 1, else 1; a NULL required pointer (x, y, ws, one f0 track
+ * without the other, some but not all per-row outputs, no output at all) 3; both before anything touches a device. */
+long long v100_dtw_workspace_bytes(int B, int Tx, int Ty, int D, int want_path);
+int v100_dtw_score(const float* x, const int* x_len, const float* y, const int* y_len, const float* f0x, const float* f0y, void* ws,
+                   double* cost, int* path_len, int* voiced, int* vuv_errors, double* f0_sq_cents, double* f0_sq_hz, int* path,
+                   double* totals, int B, int Tx, int Ty, int D, int skip, float f0_floor, int mode, void* stream);
 /* TextToAlignTextModel.align (voice100/models/tts.py:89-110) batched: text [B][Lmax] int64, align [B][Lmax][2] float64
  * (gap, length), out [B][Tmax] int64 (zero padded; rows longer than Tmax are cut), out_len [B].  out == NULL: only out_len is
  * written (head + int(sum(align)) + tail per utterance), so the caller can size `out` with one read-back. */

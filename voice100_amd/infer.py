@@ -105,6 +105,33 @@ def scatter_run(fn: Callable[..., Sequence[torch.Tensor]], inputs: Sequence[torc
     return result if rank == 0 else None
 
 
+@torch.no_grad()
+def _tts_score(self, text: torch.Tensor, text_len: torch.Tensor, ref_f0: torch.Tensor, ref_feat: torch.Tensor, ref_frames: torch.Tensor,
+               meter=None):
+    """Objective scores of the pipeline's output against a recording's WORLD features (metrics.dtw_score, K27): the chain of
+    __call__ with the synthesis off, then the DTW of its f0 / features / frames with ref_f0 [B, Tr] Hz, ref_feat [B, Tr, C] and
+    ref_frames [B].  The distance is taken on mel-cepstra without c0: the audio model's own output where it predicts mel-cepstra,
+    its log-spectrum through sp2mc otherwise (SynthesisScore.to_mcep; the same for ref_feat).  Returns {"score": the per-utterance
+    metrics.DTWScore, "mcd" [B] float64 dB (nan for an empty pair), "frames" [B]}; no read-back.  meter: a metrics.SynthesisScore
+    that also takes the batch's sums."""
+    from .metrics import SynthesisScore, mcd_db
+    out, feat = self._run(text, text_len, False)
+    dev = feat.device
+    m = meter if meter is not None else SynthesisScore(self.vocoder)
+    sc = m.update(out["f0"], feat, out["frames"], ref_f0.to(dev), ref_feat.to(dev), ref_frames.to(dev), per_row=True)
+    return {"score": sc, "mcd": mcd_db(sc.cost, sc.path_len), "frames": out["frames"]}
+
+
+def _tts_evaluate(self, batches, meter=None):
+    """Scores over an iterable of (text, text_len, ref_f0, ref_feat, ref_frames): score() per batch into one meter, and ONE
+    device-to-host synchronisation at the end.  Returns SynthesisScore.compute()."""
+    from .metrics import SynthesisScore
+    meter = meter if meter is not None else SynthesisScore(self.vocoder)
+    for text, text_len, ref_f0, ref_feat, ref_frames in batches:
+        self.score(text, text_len, ref_f0, ref_feat, ref_frames, meter)
+    return meter.compute()
+
+
 class TTSPipeline:
     """BASELINE configs[2] end to end on the device (update_samples.py:46-84, the pyworld synthesis included):
 
@@ -132,6 +159,12 @@ class TTSPipeline:
 
     @torch.no_grad()
     def __call__(self, text: torch.Tensor, text_len: torch.Tensor):
+        return self._run(text, text_len, self.synthesize)[0]
+
+    score, evaluate = _tts_score, _tts_evaluate
+
+    def _run(self, text: torch.Tensor, text_len: torch.Tensor, synthesize: bool):
+        """The chain of __call__: its result, and the audio model's own features (mel-cepstra with a use_mcep vocoder)."""
         from .decode import align_expand
         pred = self.align_model(text)                                        # [B, L, 2]
         align = torch.clamp_min(torch.exp(pred) - 1.0, 0.0)
@@ -155,11 +188,11 @@ class TTSPipeline:
                "codeap": codeap, "frames": frames}
         if extra:
             out["phone_logits"] = extra[0]
-        if v is not None and self.synthesize and v.n_fft == 512 and f0.shape[1] >= 2:
+        if v is not None and synthesize and v.n_fft == 512 and f0.shape[1] >= 2:
             wave, npulses = v.synthesize(f0, spc, frames=frames, f0_ceil=self.f0_ceil, codeap=codeap)
             out["wave"], out["n_pulses"] = wave, npulses
             out["wave_len"] = (frames.to(torch.float64) * v.frame_period * v.sample_rate / 1000).to(torch.int64)
-        return out
+        return out, feat
 
 
 class TTSPipelineV2:
@@ -183,6 +216,12 @@ class TTSPipelineV2:
 
     @torch.no_grad()
     def __call__(self, text: torch.Tensor, text_len: torch.Tensor):
+        return self._run(text, text_len, self.synthesize)[0]
+
+    score, evaluate = _tts_score, _tts_evaluate
+
+    def _run(self, text: torch.Tensor, text_len: torch.Tensor, synthesize: bool):
+        """The chain of __call__: its result, and the audio model's own features (mel-cepstra with a use_mcep vocoder)."""
         from .decode import align_expand_v2
         align, align_len = self.align_model.predict(text, text_len)         # [B, max(text_len), 2]
         L = align.shape[1]
@@ -198,11 +237,11 @@ class TTSPipelineV2:
         frames = torch.clamp_max(2 * at_len, f0.shape[1])
         out = {"align": align, "aligntext": aligntext, "aligntext_len": at_len, "f0": f0, "logspc": logspc, "spc": spc,
                "codeap": codeap, "frames": frames}
-        if v is not None and self.synthesize and v.n_fft == 512 and f0.shape[1] >= 2:
+        if v is not None and synthesize and v.n_fft == 512 and f0.shape[1] >= 2:
             wave, npulses = v.synthesize(f0, spc, frames=frames, f0_ceil=self.f0_ceil, codeap=codeap)
             out["wave"], out["n_pulses"] = wave, npulses
             out["wave_len"] = (frames.to(torch.float64) * v.frame_period * v.sample_rate / 1000).to(torch.int64)
-        return out
+        return out, feat
 
 
 class ASRPipeline:
