@@ -768,6 +768,25 @@ int v100_resample_tile(void);
 int v100_resample_sinc(const float* x, const int* lens, const float* taps, const int* starts, float* y, int* out_lens, int B,
                        int Nmax, int Mmax, int o, int n, int width, int L, void* stream);
 
+/* ---- K28 FLAC decoding (csrc/flac.hip): the frame regions of B FLAC files -> PCM, four launches and no read-back.
+ * bytes [nbytes] uint8 on the device: the files' frame regions (everything from the first frame on), each beginning on a multiple of
+ * 16 and followed by zero bytes up to the next multiple of 16 plus 16 more; nbytes a multiple of 16, 16 <= nbytes < 2^31.
+ * table [B][16] int32 on the device, per file: {byte begin, byte end (exclusive), channels, bits per sample, minimum and maximum block
+ * size, total samples, output row, first slot, slots, first table entry, table entries (a power of two >= 2 slots), first staging int,
+ * 0, 0, 0}; slots bounds the frame candidates of the file (total samples / minimum block size plus slack), its staging area is
+ * slots x channels x maximum block size ints.  S, H, stage_ints: the sums over the files; max_file_bytes: the longest frame region.
+ * ws: v100_flac_workspace_bytes(B, S, H, stage_ints) bytes (-1 = unsupported).
+ * Outputs: wave [B][Cw][Nmax] fp32 = sample / 2^(bits - 1), Cw == 1: channel 0 only; pcm [B][Cp][Nmax] int32 or NULL; both are written
+ * inside each file's total samples only (the caller zeroes them); lengths [B] int32 = total samples; status [B][2] int32 = {0, frames}
+ * or {code, where}: 1 more frame candidates than slots (where = byte offset), 2 no frame where frame `where` must begin, 3 a reserved
+ * code in frame `where`, 4 that frame runs past the file's end, 5 its CRC-16 does not match, 6 its sample position does not follow,
+ * 7 it passes total samples, 8 the file ends after `where` frames short of total samples.  A frame counts only on the chain that
+ * starts at `begin`; no input bytes, however corrupt, make the kernels read or write outside the buffers described here.
+ * 1 on a bad shape; 3 on a NULL pointer (pcm may be NULL). */
+long long v100_flac_workspace_bytes(int B, int S, int H, long long stage_ints);
+int v100_flac_decode(const unsigned char* bytes, long long nbytes, const int* table, void* ws, float* wave, int* pcm, int* lengths,
+                     int* status, int B, int S, int H, long long stage_ints, int max_file_bytes, int Cw, int Cp, int Nmax, void* stream);
+
 /* ---- K19 WORLD feature statistics (csrc/world_stat.hip): one accumulation step of voice100/calc_stat.py:40-56 over a padded batch.
  * f0 [B][T], logspc [B][T][S], codeap [B][T][A] fp32, f0_len [B] int32, all on the device and contiguous (4-byte alignment is
  * enough).  Frame (b, t) is valid iff t < min(max(f0_len[b], 0), T).  The call ADDS to moments, float64 [4 + 2S + 2A]:

@@ -1,12 +1,16 @@
-"""From an audio file to a waveform at the model's rate, without torchaudio: a RIFF/WAVE reader on the host and
+"""From an audio file to a waveform at the model's rate, without torchaudio: a RIFF/WAVE reader on the host, a FLAC decoder on the
+GPU (csrc/flac.hip: the container is parsed on the host, the frames are found, decoded, chained and committed on the device) and
 `torchaudio.functional.resample`'s default method on the GPU (csrc/resample.hip).
 
 The reference opens files with `torchaudio.load` + `torchaudio.functional.resample` (data_modules.py:287-292) or with sox effects
 (`remix 1`, `rate`: data_modules.py:295-316).  `load_wav` returns what `torchaudio.load` returns for a WAV file with its defaults;
 `resample` follows the published definition of `sinc_interpolation` with a Hann window, its filter bank built in float64 and
 rounded to float32 once (torchaudio builds it in float32: a few ulps per tap apart).  PARITY UNPINNED against torchaudio itself
-(absent here): checked against a float64 restatement of that definition.  FLAC (LibriSpeech) and every compressed format are out
-of scope -- decode those with a decoder of your own and pass the tensor.
+(absent here): checked against a float64 restatement of that definition.  `load_flac` returns what `torchaudio.load` returns for a
+native FLAC file (LibriSpeech's format; 8 to 24 bits, 1 to 8 channels), `load_audio` picks between the two by the file's first bytes,
+and `load_batch` takes either.  FLAC parity with libFLAC rests on the three worked examples of the format's RFC until real files
+exist under tests/golden/flac.  Out of scope: Ogg-FLAC, files with a leading ID3 tag, FLAC of unknown length, 32-bit FLAC and every
+lossy format.
 """
 import math
 import struct
@@ -89,6 +93,203 @@ def load_wav(path):
             return torch.from_numpy(np.ascontiguousarray(samples.reshape(frames, channels).T)), int(rate)
         pos = body + size + (size & 1)
     raise ValueError(f"{path}: RIFF/WAVE file without a `data` chunk" + ("" if fmt else " or a `fmt ` chunk") + " (truncated?)")
+
+
+# ---- FLAC: the container on the host, the frames on the device (csrc/flac.hip) ---------------------------------------------------
+FlacInfo = namedtuple("FlacInfo", "sample_rate channels bits_per_sample total_samples min_blocksize max_blocksize md5 first_frame_offset")
+FlacInfo.__doc__ = """STREAMINFO of a FLAC file, and the byte at which its first frame begins.  md5: 16 bytes, all zero = unknown."""
+
+_FLAC_STATUS = {
+    1: "more frame headers than its STREAMINFO allows for (near byte {w} of the frames)",
+    2: "no valid frame header where frame {w} must begin (missing, cut off, or damaged)",
+    3: "frame {w} holds a reserved code",
+    4: "frame {w} runs past the end of the file (truncated?)",
+    5: "frame {w} fails its CRC-16 (damaged data)",
+    6: "frame {w} is not at the sample position that follows the frame before it (a frame is missing)",
+    7: "frame {w} passes the total_samples of STREAMINFO",
+    8: "the file ends after {w} frames, short of the total_samples of STREAMINFO",
+}
+
+
+def _flac_bytes(src):
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        return bytes(src), "<bytes>"
+    with open(src, "rb") as f:
+        return f.read(), str(src)
+
+
+def _flac_info(data: bytes, what: str) -> FlacInfo:
+    if data[:4] == b"OggS":
+        raise ValueError(f"{what}: an Ogg container (Ogg-FLAC is not read; native FLAC begins b'fLaC')")
+    if data[:3] == b"ID3":
+        raise ValueError(f"{what}: a leading ID3 tag (strip it; native FLAC begins b'fLaC')")
+    if data[:4] != b"fLaC":
+        raise ValueError(f"{what}: not a FLAC file (it begins {data[:4]!r})")
+    pos, info = 4, None
+    while True:
+        if pos + 4 > len(data):
+            raise ValueError(f"{what}: truncated FLAC metadata (a block header at byte {pos}, the file has {len(data)})")
+        last, typ, size = data[pos] >> 7, data[pos] & 0x7F, int.from_bytes(data[pos + 1:pos + 4], "big")
+        if pos + 4 + size > len(data):
+            raise ValueError(f"{what}: truncated FLAC metadata (block type {typ} at byte {pos} declares {size} bytes, "
+                             f"{len(data) - pos - 4} in the file)")
+        if pos == 4 and (typ != 0 or size != 34):
+            raise ValueError(f"{what}: the first metadata block is type {typ} with {size} bytes, not STREAMINFO (type 0, 34 bytes)")
+        if typ == 0 and info is None:
+            b = data[pos + 4:pos + 38]
+            x = int.from_bytes(b[10:18], "big")
+            info = (x >> 44, ((x >> 41) & 7) + 1, ((x >> 36) & 31) + 1, x & ((1 << 36) - 1),
+                    int.from_bytes(b[0:2], "big"), int.from_bytes(b[2:4], "big"), bytes(b[18:34]))
+        pos += 4 + size
+        if last:
+            break
+    rate, channels, bits, total, lo, hi, md5 = info
+    if total == 0:
+        raise ValueError(f"{what}: STREAMINFO gives total_samples 0 (length unknown): not decoded")
+    if bits == 32:
+        raise ValueError(f"{what}: 32 bits per sample (a side channel would need 33): not decoded")
+    if bits < 4 or channels > 8:
+        raise ValueError(f"{what}: {channels} channels of {bits} bits per sample: not decoded")
+    if total >= 2 ** 31:
+        raise ValueError(f"{what}: {total} samples: sample positions pass 2^31, not decoded")
+    if lo < 1 or hi < lo:
+        raise ValueError(f"{what}: STREAMINFO gives block sizes {lo} to {hi}")
+    if rate < 1:
+        raise ValueError(f"{what}: STREAMINFO gives a sample rate of {rate} Hz")
+    return FlacInfo(rate, channels, bits, total, lo, hi, md5, pos)
+
+
+def flac_info(path_or_bytes) -> FlacInfo:
+    """The STREAMINFO block of a native FLAC file (a path, or its bytes) and where its frames begin; needs no GPU.  ValueError naming
+    what was found for: a file that is not FLAC, Ogg-FLAC, a leading ID3 tag, a truncated metadata chain, total_samples 0 (length
+    unknown), 32 bits per sample, and a file so long that sample positions pass 2^31."""
+    return _flac_info(*_flac_bytes(path_or_bytes))
+
+
+_FLAC_WS_LIMIT = 2 ** 31 - 1                                           # staging ints one call indexes
+
+
+def _flac_plan(datas, infos, names):
+    """The byte buffer and the per-file table v100_flac_decode takes (numpy, host only): (buffer uint8, table [B][16] int32, S, H,
+    stage_ints, max_file_bytes)."""
+    B = len(datas)
+    table = np.zeros((B, 16), np.int32)
+    chunks, at, slot, entry, stage, longest = [], 0, 0, 0, 0, 1
+    for b, (data, fi) in enumerate(zip(datas, infos)):
+        region = data[fi.first_frame_offset:]
+        frames = -(-fi.total_samples // fi.min_blocksize)
+        slots = frames + 8 + frames // 8                              # every true frame, and slack for payload bytes that spell a header
+        entries = 1 << max(4, (2 * slots - 1).bit_length())
+        table[b, :13] = (at, at + len(region), fi.channels, fi.bits_per_sample, fi.min_blocksize, fi.max_blocksize, fi.total_samples, b,
+                         slot, slots, entry, entries, stage)
+        padded = -(-len(region) // 16) * 16 + 16
+        chunks.append(np.frombuffer(region, np.uint8))
+        chunks.append(np.zeros(padded - len(region), np.uint8))
+        at, slot, entry, longest = at + padded, slot + slots, entry + entries, max(longest, len(region))
+        stage += slots * fi.channels * fi.max_blocksize
+        if stage > _FLAC_WS_LIMIT or at > _FLAC_WS_LIMIT or slot >= 2 ** 26 or entry >= 2 ** 27:
+            raise ValueError(f"decode_flac: the batch needs more workspace than one call indexes (at {names[b]}: {fi.total_samples} samples "
+                             f"in blocks of {fi.min_blocksize} to {fi.max_blocksize}); decode fewer files per call")
+    return np.concatenate(chunks), table, slot, entry, stage, longest
+
+
+@torch.no_grad()
+def _flac_decode_device(files, device, channels, want_pcm):
+    """decode_flac up to and including the read-back of the status: (wave, lengths, pcm or None, status [B][2] numpy, names, infos)."""
+    if channels not in ("first", "all"):
+        raise ValueError(f"decode_flac: channels must be 'first' or 'all' (got {channels!r})")
+    files = list(files)
+    if not files:
+        raise ValueError("decode_flac: no files")
+    datas, names, infos = [], [], []
+    for k, src in enumerate(files):
+        data, name = _flac_bytes(src)
+        name = f"<bytes #{k}>" if name == "<bytes>" else name
+        datas.append(data)
+        names.append(name)
+        infos.append(_flac_info(data, name))
+    if not torch.cuda.is_available():
+        raise RuntimeError("decode_flac: voice100_amd runs on the GPU only (no CPU fallback): FLAC frames are decoded on the device")
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"decode_flac: voice100_amd runs on the GPU only (got device {device})")
+    buf, table, S, H, stage_ints, longest = _flac_plan(datas, infos, names)
+    B = len(files)
+    Nmax = max(fi.total_samples for fi in infos)
+    Cmax = max(fi.channels for fi in infos)
+    Cw = 1 if channels == "first" else Cmax
+    with torch.cuda.device(device):
+        ws_bytes = int(N.helper("v100_flac_workspace_bytes", B, S, H, stage_ints))
+        if ws_bytes < 0:
+            raise ValueError(f"decode_flac: unsupported batch ({B} files, {S} frame slots)")
+        d_buf = torch.from_numpy(buf).to(device)
+        d_table = torch.from_numpy(table).to(device)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+        wave = torch.zeros((B, Nmax) if channels == "first" else (B, Cw, Nmax), dtype=torch.float32, device=device)
+        pcm = torch.zeros((B, Cmax, Nmax), dtype=torch.int32, device=device) if want_pcm else None
+        lengths = torch.empty((B,), dtype=torch.int32, device=device)
+        status = torch.empty((B, 2), dtype=torch.int32, device=device)
+        N.call("v100_flac_decode", d_buf, int(buf.size), d_table, ws, wave, pcm, lengths, status, B, S, H, stage_ints, longest, Cw, Cmax,
+               Nmax)
+        st = status.cpu().numpy()
+    return wave, lengths, pcm, st, names, infos
+
+
+@torch.no_grad()
+def decode_flac(files, device=None, channels="first", verify_md5=False, return_pcm=False):
+    """A list of FLAC files (paths, or their bytes) -> (wave, lengths, rates), decoded on the GPU in one pass (csrc/flac.hip).
+
+    wave [B, Nmax] float32 on the device = channel 0 of each file (`channels="first"`), or [B, Cmax, Nmax] with every channel
+    (`channels="all"`; rows of files with fewer channels stay zero); the sample value is int / 2^(bits - 1), as `torchaudio.load`
+    normalises; exact zeros beyond each file's length.  lengths [B] int32 on the device, rates a list of ints.  With `return_pcm`
+    a fourth value: the integer samples [B, Cmax, Nmax] int32 on the device.
+
+    The container is parsed on the host (`flac_info`), the frame regions go to the device in one copy, four launches find, decode,
+    chain and commit the frames, and ONE read-back brings the per-file status: a file that does not decode cleanly -- a damaged,
+    truncated or missing frame, a sample count that disagrees with STREAMINFO -- is a ValueError naming the file, the frame and the
+    reason.  `verify_md5` also reads the integer PCM back and compares the MD5 of the interleaved little-endian samples (whole
+    bytes per sample) with STREAMINFO's; an all-zero MD5 is skipped.  Files of different rates, widths, channel counts and lengths
+    mix freely.  No CPU fallback."""
+    wave, lengths, pcm, st, names, infos = _flac_decode_device(files, device, channels, bool(return_pcm or verify_md5))
+    B = len(names)
+    for b in range(B):
+        code, where = int(st[b, 0]), int(st[b, 1])
+        if code:
+            raise ValueError(f"{names[b]}: FLAC " + _FLAC_STATUS.get(code, f"status {code} at {{w}}").format(w=where))
+    if verify_md5:
+        import hashlib
+        host = pcm.cpu().numpy()
+        for b, fi in enumerate(infos):
+            if fi.md5 == bytes(16):
+                continue
+            nb = (fi.bits_per_sample + 7) // 8
+            inter = np.ascontiguousarray(host[b, :fi.channels, :fi.total_samples].T).reshape(-1)
+            raw = inter.astype("<i4").view(np.uint8).reshape(-1, 4)[:, :nb]
+            got = hashlib.md5(np.ascontiguousarray(raw).tobytes()).digest()
+            if got != fi.md5:
+                raise ValueError(f"{names[b]}: FLAC MD5 mismatch (decoded {got.hex()}, STREAMINFO says {fi.md5.hex()})")
+    rates = [fi.sample_rate for fi in infos]
+    return (wave, lengths, rates, pcm) if return_pcm else (wave, lengths, rates)
+
+
+def load_flac(path, verify_md5=False):
+    """(waveform [channels, frames] float32 CPU tensor, sample_rate): `torchaudio.load(path)` with its defaults, for a FLAC file.
+    The frames are decoded on the GPU (`decode_flac`): without one this is a RuntimeError; `flac_info` works without."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("load_flac: voice100_amd runs on the GPU only (no CPU fallback): FLAC frames are decoded on the device")
+    wave, _, rates = decode_flac([path], channels="all", verify_md5=verify_md5)
+    return wave[0].cpu(), int(rates[0])
+
+
+def load_audio(path):
+    """`load_wav` or `load_flac`, by the file's first four bytes (b'RIFF' / b'fLaC'); anything else is a ValueError naming them."""
+    with open(path, "rb") as f:
+        magic = f.read(4)
+    if magic == b"RIFF":
+        return load_wav(path)
+    if magic == b"fLaC":
+        return load_flac(path)
+    raise ValueError(f"{path}: neither WAV nor FLAC (it begins {magic!r}; b'RIFF' and b'fLaC' are read)")
 
 
 # ---- the filter bank --------------------------------------------------------------------------------------------------------
@@ -205,11 +406,13 @@ def resample(waveform: torch.Tensor, orig_freq, new_freq, lengths=None, lowpass_
 
 
 def load_batch(paths, sample_rate, device=None):
-    """A list of WAV files -> (wave [B, Mmax] float32, zero beyond each utterance, wave_len [B] int32), both on the device, in
+    """A list of WAV and / or FLAC files -> (wave [B, Mmax] float32, zero beyond each utterance, wave_len [B] int32), both on the device, in
     the order of `paths`: per file what the reference's transforms do (load, first channel, resample to `sample_rate`:
     data_modules.py:287-292), row b equal to resample(load_wav(paths[b])[0][0], its rate, sample_rate).  The files are grouped by
     their own rate; a group is one padded block, one host-to-device copy and one resample(..., lengths=) launch, and its rows
-    are scattered to their places by one indexed copy.  Files already at `sample_rate` are copied through."""
+    are scattered to their places by one indexed copy.  Files already at `sample_rate` are copied through.  The FLAC files among
+    `paths` are decoded together in ONE device pass (decode_flac), whatever their rates, and their rows join the group of their rate
+    on the device; WAV rows and all-WAV batches go exactly the way they went before FLAC was read."""
     if not torch.cuda.is_available():
         raise RuntimeError("load_batch: voice100_amd runs on the GPU only (no CPU fallback): the resampling runs on the device")
     paths = list(paths)
@@ -220,20 +423,49 @@ def load_batch(paths, sample_rate, device=None):
         raise RuntimeError(f"load_batch: voice100_amd runs on the GPU only (got device {device})")
     _rates(sample_rate, sample_rate)                                  # a positive integer, or ValueError
     target = int(sample_rate)
-    groups = {}                                                       # source rate -> [(row, first channel)]
+    groups = {}                                                       # source rate -> [(row, first channel)]: WAV rows, on the host
+    flac_rows, flac_data = [], []
     for row, path in enumerate(paths):
+        with open(path, "rb") as f:
+            is_flac = f.read(4) == b"fLaC"
+            if is_flac:
+                flac_rows.append(row)
+                flac_data.append(b"fLaC" + f.read())
+        if is_flac:
+            continue
         waveform, sr = load_wav(path)
         if waveform.shape[1] < 1:
             raise ValueError(f"{path}: no samples")
         groups.setdefault(sr, []).append((row, waveform[0]))
+    flac_groups = {}                                                  # source rate -> [(row, index into the decoded block, length)]
+    if flac_rows:
+        try:
+            f_wave, _, f_rates = decode_flac(flac_data, device)       # every FLAC file of the batch in one device pass
+        except ValueError as e:                                       # name the path, not the position among the FLAC files
+            msg = str(e)
+            for k, row in enumerate(flac_rows):
+                msg = msg.replace(f"<bytes #{k}>", str(paths[row]))
+            raise ValueError(msg) from None
+        f_lens = [flac_info(d).total_samples for d in flac_data]
+        for k, row in enumerate(flac_rows):
+            flac_groups.setdefault(f_rates[k], []).append((row, k, f_lens[k]))
+            groups.setdefault(f_rates[k], [])
     done = []                                                         # (rows, y [G, M], y_len [G])
     for sr, items in groups.items():
-        rows = torch.tensor([r for r, _ in items], dtype=torch.int64)
-        lens = torch.tensor([w.shape[0] for _, w in items], dtype=torch.int32)
-        block = torch.zeros((len(items), int(lens.max())), dtype=torch.float32)
+        fitems = flac_groups.get(sr, [])
+        rows = torch.tensor([r for r, _ in items] + [r for r, _, _ in fitems], dtype=torch.int64)
+        lens = torch.tensor([w.shape[0] for _, w in items] + [n for _, _, n in fitems], dtype=torch.int32)
+        width = int(lens.max())
+        block = torch.zeros((len(items), width), dtype=torch.float32)
         for g, (_, w) in enumerate(items):
             block[g, :w.shape[0]] = w
-        y, y_len = resample(block.to(device), sr, target, lengths=lens)
+        block = block.to(device)
+        if fitems:                                                    # the decoded rows are on the device already
+            take = min(width, f_wave.shape[1])
+            fblock = torch.zeros((len(fitems), width), dtype=torch.float32, device=device)
+            fblock[:, :take] = f_wave[torch.tensor([k for _, k, _ in fitems], device=device), :take]
+            block = torch.cat([block, fblock]) if items else fblock
+        y, y_len = resample(block, sr, target, lengths=lens)
         done.append((rows.to(device), y, y_len))
     B, width = len(paths), max(y.shape[1] for _, y, _ in done)
     wave = torch.zeros((B, width), dtype=torch.float32, device=device)
@@ -247,7 +479,7 @@ def load_batch(paths, sample_rate, device=None):
 class WORLDAudioProcessor(nn.Module):
     """voice100's WORLDAudioProcessor (data_modules.py:295-316): a file path -> (f0, logspc or mcep, codeap), float32 CPU tensors
     as `WORLDVocoder.encode` returns them.  The reference reads the file through sox (`remix 1`: the first channel; `rate`: to
-    `sample_rate`); here `load_wav` reads it and `resample` converts the rate.  sox's `rate` effect is a different low-pass filter
+    `sample_rate`); here `load_audio` reads it (WAV or FLAC) and `resample` converts the rate.  sox's `rate` effect is a different low-pass filter
     from torchaudio's windowed sinc, so the features are those of this library's resampler, not sample-equal to a sox run --
     unpinned, like the rest of the WORLD analysis."""
 
@@ -264,6 +496,6 @@ class WORLDAudioProcessor(nn.Module):
     def forward(self, audiopath):
         if not torch.cuda.is_available():
             raise RuntimeError("WORLDAudioProcessor runs on the GPU only (no CPU fallback)")
-        waveform, sr = load_wav(audiopath)
+        waveform, sr = load_audio(audiopath)
         x = resample(waveform[0].to(torch.device("cuda", torch.cuda.current_device())), sr, self.sample_rate)
         return self.vocoder.encode(x)

@@ -101,7 +101,7 @@ class WorldAlignTextCollate:
     AlignTextToAudioMultiTaskModel train on.  Features are padded with 0, ids with BLANK_IDX; dtypes are the reference's.
     `audio` is, the same for every item of a batch, one of
 
-    * a path to a WAV file: audio_io.load_batch, then ONE WORLDVocoder.encode_batch(wave, wave_len) over the whole batch;
+    * a path to a WAV or FLAC file: audio_io.load_batch, then ONE WORLDVocoder.encode_batch(wave, wave_len) over the whole batch;
     * a 1-D waveform tensor at the vocoder's sample rate: padded to one block, then the same call;
     * an already computed `(f0 [T], spec [T, D], codeap [T, nb])` triple -- what the reference's feature cache hands its collate.
       This path is pure pad_sequence, needs no GPU and leaves the batch where the tensors are.

@@ -308,7 +308,7 @@ class ASRPipeline:
         return self._beam(logits, out_len, self.nbest_size)
 
     def transcribe(self, paths, decode: Callable[[torch.Tensor], str]) -> List[str]:
-        """WAV files -> their transcripts: audio_io.load_batch, the ragged pipeline, then `decode` (the caller's tokenizer.decode,
+        """WAV or FLAC files -> their transcripts: audio_io.load_batch, the ragged pipeline, then `decode` (the caller's tokenizer.decode,
         ids tensor -> str, as in align_records) on each row's ids; one device-to-host copy per tensor.  Needs a `mel`."""
         from .audio_io import load_batch
         if self.mel is None:

@@ -6,7 +6,7 @@ n_fft, power 2, HTK mel scale, no norm) followed by log(mel.T + 1e-6).
 The framed real DFT is a dense [2*257 x 400] x [400 x T] product (window folded into the basis) and the
 filterbank a [64 x 257] x [257 x T] one; both run on the exact-fp32 MFMA GEMM kernel, with three small
 HBM-bound kernels around them (framing, power, log+transpose).  A file path is decoded on the host by
-audio_io.load_wav (WAV only) and brought to the module's rate on the GPU by audio_io.resample: no torchaudio.
+audio_io.load_audio (WAV on the host, FLAC on the GPU) and brought to the module's rate on the GPU by audio_io.resample: no torchaudio.
 PARITY UNPINNED against torchaudio itself (absent here): checked against oracle/mel.py and torch.stft.
 """
 import math
@@ -170,13 +170,13 @@ class MelSpectrogramAudioTransform(nn.Module):
         return out, out_len
 
     def forward(self, audio):
-        """A path to a WAV file (as in the reference: load, first channel, resample to the module's rate, transform) or an
+        """A path to a WAV or FLAC file (as in the reference: load, first channel, resample to the module's rate, transform) or an
         already-loaded waveform tensor.  A list or tuple of paths gives the padded batch and its lengths,
         transform(*audio_io.load_batch(paths, sample_rate)).  The module must be on the GPU: the resampling runs there too."""
         if isinstance(audio, torch.Tensor):
             return self.transform(audio)
-        from .audio_io import load_batch, load_wav, resample
+        from .audio_io import load_audio, load_batch, resample
         if isinstance(audio, (list, tuple)):
             return self.transform(*load_batch(audio, self.sample_rate, self.dft_basis.device))
-        waveform, sr = load_wav(audio)
+        waveform, sr = load_audio(audio)
         return self.transform(resample(waveform[0].to(self.dft_basis.device), sr, self.sample_rate))
