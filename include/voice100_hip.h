@@ -530,6 +530,22 @@ long long v100_ctc_align_workspace_bytes(int B, int T, int Lmax);
 int v100_ctc_align_block(void);
 int v100_ctc_align(const float* logp, const long long* labels, const int* in_len, const int* lab_len, void* moves_ws, int* path,
                    long long* best_labels, int* align, float* score, int B, int T, int V, int Lmax, int max_move, void* stream);
+/* K29, forced alignment of long recordings in one launch (csrc/align_long.hip): a banded Viterbi over the CTC topology (stay, advance,
+ * skip a blank between two different labels; first maximum wins; one fp32 add per frame and state).  logp [B][T][V] log-probabilities,
+ * labels [B][Lmax] int64, in_len / lab_len [B] or NULL (clamped to [.., T] / [0, Lmax] on the device), free_logp [B][T] or NULL:
+ * what the first and the last extended position emit instead of the blank's log-probability.  Only `band` consecutive positions are
+ * live; every v100_ctc_align_long_block() frames the window is re-centred on its best position (it never moves back; the two
+ * positions that emit free_logp bound every other score and do not count as the best) and the scores are renormalised into an fp64
+ * offset.  score [B] fp64; ok [B] int32 = 0 where the end position is not live in the last window (too
+ * few frames, no frame, or a band that lost the path): that row has score -inf and zeros in path and align.  path [B][T] int32 =
+ * extended positions, 0 beyond in_len; align [B][2*Lmax+1] int32 = frames per extended position, 0 beyond 2*lab_len+1.
+ * ws: v100_ctc_align_long_workspace_bytes(B, T, Lmax, band) bytes (two bits per frame and window slot, and the window's start per
+ * block; 0 = unsupported shape).  B >= 1, 1 <= T <= 2^20, 0 <= Lmax <= 2^19, V >= 2, band a multiple of 64 in [64, 8192], else 1;
+ * a NULL required pointer 3; both before anything touches a device. */
+long long v100_ctc_align_long_workspace_bytes(int B, int T, int Lmax, int band);
+int v100_ctc_align_long_block(void);
+int v100_ctc_align_long(const float* logp, const long long* labels, const int* in_len, const int* lab_len, const float* free_logp, void* ws,
+                        double* score, int* ok, int* path, int* align, int B, int T, int V, int Lmax, int band, int blank, void* stream);
 /* K23, batched edit distance (csrc/edit_distance.hip): the Levenshtein distance (unit costs for substitution, insertion and
  * deletion) between hyp [B][Th] int64 and ref [B][Tr] int64, rows of hyp_len / ref_len [B] int32 ids (clamped to [0, width] on the
  * device; nothing beyond a row's length is read; ids compare on all 64 bits).  levels: 1 = id level (a token is one id), 2 = word

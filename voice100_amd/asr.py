@@ -42,6 +42,15 @@ class ConvVoiceEncoder(nn.Module):
             return F_.ir_stack_train(self.layers, embed)      # the nine blocks through the stack executor: one host call per direction
         return self.layers(embed)
 
+    def receptive_field(self):
+        """(field, halo, stride) from the layer list: one output frame depends on `field` consecutive input frames, `halo` of them on
+        each side of the frame at `stride` times its index (every block pads (k - 1) // 2 on both sides, so the field is centred)."""
+        halo, jump = 0, 1
+        for blk in self.layers:
+            halo += (int(blk.kernel_size) - 1) // 2 * jump
+            jump *= int(blk.stride)
+        return 2 * halo + 1, halo, jump
+
     def output_length(self, embed_len: torch.Tensor) -> torch.Tensor:
         half = F_.half_length(embed_len)          # the augmentation pass already wrote (len + 1) // 2 next to the lengths
         if half is not None:
@@ -127,6 +136,10 @@ class AudioToTextCTC(Voice100ModelBase):
 
     def output_length(self, audio_len: torch.Tensor) -> torch.Tensor:
         return self.encoder.output_length(audio_len)
+
+    def receptive_field(self):
+        """The encoder's (field, halo, stride) in audio frames; the vocabulary head is a 1x1 convolution and adds nothing."""
+        return self.encoder.receptive_field()
 
     def normalize(self, audio: torch.Tensor, audio_len: torch.Tensor) -> torch.Tensor:
         """Masked per-utterance mean / std normalisation over time (asr.py:124-131).  Off by default in the reference

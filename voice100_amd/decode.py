@@ -6,7 +6,8 @@ TextToAlignText.align (voice100/models/_align_v2.py:48-73).  edit_distance (K23)
 ids against reference ids (character / phone and word error counts) without leaving the device.  Neither has ctc_beam_search (K24):
 the CTC prefix beam search, n best transcripts with their total log probabilities, where the reference decodes greedily, nor its
 fused form (K25): the same search with an lm.NGramLM voting inside every frame's selection, nor ctc_segment (K26): the CTC
-forward-backward over the alignments of a given transcript, reduced to time boundaries, durations and confidences per label and word."""
+forward-backward over the alignments of a given transcript, reduced to time boundaries, durations and confidences per label and word,
+nor ctc_align_long (K29): the banded Viterbi that aligns a chapter-length recording to its text."""
 import math
 from typing import NamedTuple, Optional
 
@@ -72,6 +73,65 @@ def ctc_align(log_probs: torch.Tensor, labels: torch.Tensor, input_lengths=None,
     score = torch.empty((B,), dtype=torch.float32, device=lp.device)
     N.call("v100_ctc_align", lp, labels, il, ll, moves, path, best, align, score, B, T, V, L, int(max_move))
     return score, path, best, align
+
+
+class CTCLongAlign(NamedTuple):
+    """What ctc_align_long returns."""
+    score: torch.Tensor                                  # [B] fp64: the best path's log-probability (-inf where ok is 0)
+    ok: torch.Tensor                                     # [B] int32: 1 where the end position was live in the last window
+    path: torch.Tensor                                   # [B, T] int32: extended positions, 0 beyond each input length
+    align: torch.Tensor                                  # [B, 2 L + 1] int32: frames per extended position, 0 beyond 2 * label_length + 1
+
+
+def ctc_align_long(log_probs: torch.Tensor, labels: torch.Tensor, input_lengths=None, label_lengths=None, band: int = 2048,
+                   blank: int = 0, free_ends: bool = False) -> CTCLongAlign:
+    """Forced alignment of long recordings in one launch (K29, csrc/align_long.hip): log_probs [B, T, V] fp32 (log_softmax of the
+    logits: the kernel holds no transcendentals), labels [B, L] int64 -> CTCLongAlign(score, ok, path, align) of device tensors.
+
+    A banded Viterbi over the standard CTC topology (stay, advance by one, skip the blank between two different labels; ctc_segment's
+    topology, not ctc_align's max_move rule).  Only `band` consecutive extended positions are live at a time; every 16 frames the
+    window is re-centred on its best position -- it never moves back -- and the scores are renormalised into an fp64 offset, so T
+    may be 2^20 frames and L 2^19 labels where ctc_align stops at 12000 frames and 2047 labels.  The band is a heuristic: a wrong
+    early maximum can drag the window off the true path, which then ends with ok = 0 (score -inf, path and align zero); widen `band`.
+    ok is also 0 where there are fewer frames than labels need, or no frame.  band >= 2 L + 1 is the exact Viterbi.
+    free_ends: the first and the last extended position (the blanks around the text) emit log_probs.amax(-1) instead of the blank's
+    log-probability, so a spoken preamble or outro that is not in the text can sit there.  (No path can beat a state that emits every
+    frame's best symbol, so those two positions are left out when the window looks for its best position.)
+    Lengths are clamped to [.., T] / [0, L] on the device; labels outside [0, V) read the nearest column.  Two calls give equal bits.
+    Limits: 1 <= T <= 2^20, L <= 2^19, V >= 2, 0 <= blank < V, band a multiple of 64 with 64 <= band <= 8192."""
+    given = [t for t in (log_probs, labels, input_lengths, label_lengths) if t is not None]
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in given) or log_probs is None or labels is None:
+        raise RuntimeError("ctc_align_long: GPU tensors only")
+    if log_probs.dim() != 3 or labels.dim() != 2 or labels.shape[0] != log_probs.shape[0]:
+        raise RuntimeError(f"ctc_align_long: log_probs [B, T, V] and labels [B, L] with the same B, got {list(log_probs.shape)} and "
+                           f"{list(labels.shape)}")
+    lp = log_probs.contiguous().float()
+    dev = lp.device
+    B, T, V = lp.shape
+    band, blank = int(band), int(blank)
+    labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+    il = input_lengths.to(device=dev, dtype=torch.int32).contiguous() if input_lengths is not None else None
+    ll = label_lengths.to(device=dev, dtype=torch.int32).contiguous() if label_lengths is not None else None
+    if (il is not None and il.numel() != B) or (ll is not None and ll.numel() != B):
+        raise RuntimeError(f"ctc_align_long: input_lengths and label_lengths must have {B} elements")
+    width = labels.shape[1]
+    if width == 0:                                       # no column: every row is empty
+        labels, ll = labels.new_zeros((B, 1)), torch.zeros((B,), dtype=torch.int32, device=dev)
+    L = labels.shape[1]
+    nbytes = N.helper("v100_ctc_align_long_workspace_bytes", B, T, L, band) if B >= 1 else 0
+    if nbytes <= 0 or V < 2 or not 0 <= blank < V:
+        raise RuntimeError(f"ctc_align_long: unsupported shape or argument (B = {B} >= 1, 1 <= T = {T} <= 2^20, L = {width} <= 2^19, "
+                           f"V = {V} >= 2, 0 <= blank = {blank} < V and band = {band}, a multiple of 64 in [64, 8192], are the limits)")
+    free = lp.amax(-1).contiguous() if free_ends else None
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    score = torch.empty((B,), dtype=torch.float64, device=dev)
+    ok = torch.empty((B,), dtype=torch.int32, device=dev)
+    path = torch.empty((B, T), dtype=torch.int32, device=dev)
+    align = torch.empty((B, 2 * L + 1), dtype=torch.int32, device=dev)
+    N.call("v100_ctc_align_long", lp, labels, il, ll, free, ws, score, ok, path, align, B, T, V, L, band, blank)
+    if width == 0:
+        align = align[:, :1]
+    return CTCLongAlign(score, ok, path, align)
 
 
 def align_expand(text: torch.Tensor, align: torch.Tensor, text_len=None, head: int = 5, tail: int = 5):

@@ -19,7 +19,7 @@ import torch
 import torch.distributed as dist
 
 __all__ = ["shard_indices", "scatter_run", "TTSPipeline", "TTSPipelineV2", "ASRPipeline", "AlignPipeline", "align_records",
-           "ErrorRate", "GraphedForward"]
+           "ErrorRate", "GraphedForward", "window_plan", "windowed_logits", "utterance_cuts", "LongAlignPipeline", "align_long_records"]
 
 
 def shard_indices(n_items: int, rank: int, world: int, mode: str = "contiguous") -> torch.Tensor:
@@ -484,6 +484,177 @@ def align_records(out, text: torch.Tensor, text_len: torch.Tensor, decode: Calla
         durations = " ".join(str(int(x)) for x in align[i, :2 * n + 1])
         lines.append(decode(text[i, :n]) + "|" + decode(path[i, :int(path_len[i])]) + "|" + durations)
     return lines
+
+
+def window_plan(n_frames: int, keep: int, halo: int, stride: int):
+    """How windowed_logits cuts a recording of n_frames input frames: a list of (in_start, in_end, out_skip, out_count) -- the
+    forward of input frames [in_start, in_end) gives the recording's output frames from local index out_skip on, out_count of
+    them, and the windows in order cover every output frame ((n_frames - 1) // stride + 1 of them) exactly once.  A window is `keep`
+    output frames plus `halo` input frames (rounded up to a multiple of `stride`, so that every start is one) on each side; what
+    would begin before frame 0 begins there, what would end beyond the end ends there, so those edges see the padding of the whole
+    forward."""
+    if n_frames < 1 or keep < 1 or halo < 0 or stride < 1:
+        raise ValueError("window_plan: n_frames >= 1, keep >= 1, halo >= 0 and stride >= 1 are required")
+    n_out = (n_frames - 1) // stride + 1
+    h = -(-halo // stride)                               # the halo in output frames
+    plan = []
+    for o0 in range(0, n_out, keep):
+        o1 = min(o0 + keep, n_out)
+        w0 = max(o0 - h, 0)
+        plan.append((w0 * stride, min((o0 + keep + h) * stride, n_frames), o0 - w0, o1 - o0))
+    return plan
+
+
+@torch.no_grad()
+def windowed_logits(model, feats: torch.Tensor, keep: int = 1500, halo=None, max_batch: int = 32) -> torch.Tensor:
+    """The logits [T', V] of ONE recording of any length, feats [M, audio_size], as batched forwards over equal windows (window_plan):
+    `keep` output frames each plus the encoder's halo on both sides, so a two-hour recording runs at the batch shapes the kernels
+    are tuned for and no activation grows with M.  The halo comes from model.receptive_field() (ConvVoiceEncoder derives it from
+    its layer list); with it every kept frame sees exactly the inputs the whole forward gives it, and the first and the last window
+    end where the recording does, so the result is the whole forward's up to the rounding of differently tiled kernels.  Windows
+    of equal shape go `max_batch` at a time; what cannot share a shape (the first and the last windows, typically) runs as its own
+    call.  A model without receptive_field() (the LSTM models: their state spans the recording) needs halo= in input frames, and
+    the result is then APPROXIMATE: frames near a window's edge miss the context beyond it.  Eval mode only, like AlignPipeline."""
+    if model.training:
+        raise RuntimeError("windowed_logits: the model is in training mode (call model.eval(): dropout would randomise the logits)")
+    if not feats.is_cuda:
+        raise RuntimeError("windowed_logits: GPU tensors only")
+    if feats.dim() != 2 or feats.shape[0] < 1:
+        raise RuntimeError(f"windowed_logits: feats must be [M, audio_size] with M >= 1, got {list(feats.shape)}")
+    rf = getattr(model, "receptive_field", None)
+    if halo is None:
+        if rf is None:
+            raise RuntimeError("windowed_logits: the model has no receptive_field() to take the halo from (pass halo= in input "
+                               "frames; the result is then approximate)")
+        _, halo, stride = rf()
+    elif rf is not None:
+        stride = rf()[2]
+    else:
+        stride = 4096 // int(model.output_length(torch.tensor([4096])))
+    plan = window_plan(feats.shape[0], int(keep), int(halo), int(stride))
+    groups = {}                                          # (input frames, out_skip, out_count) -> window indices
+    for w, (i0, i1, skip, count) in enumerate(plan):
+        groups.setdefault((i1 - i0, skip, count), []).append(w)
+    pieces = [None] * len(plan)
+    for (_, skip, count), ws in groups.items():
+        for c in range(0, len(ws), max_batch):
+            chunk = ws[c:c + max_batch]
+            x = torch.stack([feats[plan[w][0]:plan[w][1]] for w in chunk])
+            y = model(x)
+            for k, w in enumerate(chunk):
+                pieces[w] = y[k, skip:skip + count]
+    return torch.cat(pieces, dim=0)
+
+
+def utterance_cuts(path: torch.Tensor, frame_logp: torch.Tensor, cuts, n_labels: int, conf_window: int = 30, free_ends: bool = True):
+    """The reductions of LongAlignPipeline on one aligned recording, stock ops on whatever device the tensors are on: path [T]
+    (extended positions, non-decreasing, every label visited), frame_logp [T] (the log-probability of the path's symbol at each
+    frame), cuts = the label indices where utterances begin (ascending, the first 0) -> a float64 tensor [U, 5] of (start, end,
+    frames, mean_logp, min_window_logp) in frames.  The boundary between two utterances is the midpoint of the frames between the
+    last label of one and the first label of the next; the first utterance starts at frame 0 and the last ends at T, or with
+    free_ends at the first frame of the first label and one past the last frame of the last (what lies outside is the preamble
+    and the outro).  min_window_logp is the lowest mean of frame_logp over any conf_window consecutive frames inside the utterance
+    (the whole utterance where it is shorter): the CTC-segmentation confidence."""
+    dev = path.device
+    T = path.shape[0]
+    cuts_l = [int(c) for c in cuts]
+    U = len(cuts_l)
+    if U < 1 or cuts_l[0] != 0 or any(b <= a for a, b in zip(cuts_l, cuts_l[1:])) or cuts_l[-1] >= n_labels:
+        raise ValueError("utterance_cuts: cuts must be ascending label indices that begin with 0 and stay below the number of labels")
+    cuts_t = torch.tensor(cuts_l, dtype=torch.int64, device=dev)
+    p = path.to(torch.int64).contiguous()
+    first = torch.searchsorted(p, 2 * cuts_t + 1)                                      # first frame of each utterance's first label
+    last_lab = torch.cat([cuts_t[1:] - 1, torch.tensor([n_labels - 1], dtype=torch.int64, device=dev)])
+    last = torch.searchsorted(p, 2 * last_lab + 1, right=True)                         # one past the last frame of its last label
+    mid = torch.div(last[:-1] + first[1:], 2, rounding_mode="floor")
+    lo_edge = first[:1] if free_ends else torch.zeros(1, dtype=torch.int64, device=dev)
+    hi_edge = last[-1:] if free_ends else torch.full((1,), T, dtype=torch.int64, device=dev)
+    start, end = torch.cat([lo_edge, mid]), torch.cat([mid, hi_edge])
+    frames = end - start
+    cs = torch.cat([torch.zeros(1, dtype=torch.float64, device=dev), torch.cumsum(frame_logp.to(torch.float64), 0)])
+    nz = frames.clamp_min(1).to(torch.float64)
+    mean = (cs[end] - cs[start]) / nz
+    cw = torch.minimum(frames, torch.full_like(frames, int(conf_window))).clamp_min(1)  # a short utterance is one window
+    t = torch.arange(T, dtype=torch.int64, device=dev)
+    uid = (torch.searchsorted(start, t, right=True) - 1).clamp_min(0)                   # the utterance a window starting at t belongs to
+    w_end = t + cw[uid]
+    inside = (t >= start[uid]) & (w_end <= end[uid])
+    wmean = (cs[w_end.clamp_max(T)] - cs[t]) / cw[uid].to(torch.float64)
+    wmean = torch.where(inside, wmean, torch.full_like(wmean, float("inf")))
+    wmin = torch.full((U,), float("inf"), dtype=torch.float64, device=dev).scatter_reduce(0, uid, wmean, "amin")
+    wmin = torch.where(frames > 0, wmin, mean)
+    return torch.stack([start.double(), end.double(), frames.double(), mean, wmin], dim=1)
+
+
+class LongAlignPipeline:
+    """A chapter-length recording and its text -> utterance cut points with confidences, on the device:
+
+        path or waveform
+          -> audio_io.load_batch (load_audio + resample)   the recording at the mel's sample rate
+          -> mel                                           feats [M, audio_size]
+          -> windowed_logits                               logits [T', V] from batched forwards over equal windows
+          -> torch.log_softmax                             a stock op: the kernel holds no transcendentals
+          -> decode.ctc_align_long, one launch             the banded Viterbi path over all T' frames        (K29, csrc/align_long.hip)
+          -> utterance_cuts                                gather, an fp64 cumsum, and ONE read-back
+
+    align() returns {"ok": bool, "score": float (the path's log-probability), "frame_seconds": float, "utterances": a list, one
+    entry per element of `cuts`, of {"start_s", "end_s", "frames", "mean_logp", "min_window_logp"}}.  ok False (the band lost the path
+    or the text does not fit the frames: widen `band`) comes with an empty list.  Seconds follow ASRPipeline's frame-period rule."""
+
+    def __init__(self, model, mel=None, band: int = 2048, keep: int = 1500, free_ends: bool = True, conf_window: int = 30,
+                 frame_seconds=None, blank: int = 0):
+        self.model, self.mel = model, mel
+        self.band, self.keep, self.free_ends, self.conf_window, self.blank = int(band), int(keep), bool(free_ends), int(conf_window), int(blank)
+        self.frame_seconds = frame_seconds
+
+    def _feats(self, path_or_wave):
+        if self.mel is None:
+            raise RuntimeError("LongAlignPipeline.align: the pipeline has no mel transform to turn a waveform into features (pass feats=)")
+        if isinstance(path_or_wave, torch.Tensor):
+            wave = path_or_wave.to(self.mel.dft_basis.device)
+        else:
+            from .audio_io import load_batch
+            wave = load_batch([path_or_wave], self.mel.sample_rate, self.mel.dft_basis.device)[0][0]
+        return self.mel(wave.reshape(1, -1))[0]
+
+    @torch.no_grad()
+    def align(self, path_or_wave, text_ids, cuts, feats: torch.Tensor = None):
+        """path_or_wave: a WAV / FLAC file, or a waveform [N] at the mel's sample rate; or feats [M, audio_size] directly.
+        text_ids: the whole text's label ids ([L], a tensor or a sequence); cuts: the label indices where utterances begin."""
+        from .decode import ctc_align_long
+        frame_seconds = ASRPipeline(self.model, self.mel, frame_seconds=self.frame_seconds)._frame_seconds("align")
+        if feats is None:
+            feats = self._feats(path_or_wave)
+        logits = windowed_logits(self.model, feats, self.keep)
+        lp = torch.log_softmax(logits.float(), dim=-1)
+        dev = lp.device
+        text = torch.as_tensor(text_ids, dtype=torch.int64).to(dev).reshape(1, -1)
+        L = text.shape[1]
+        res = ctc_align_long(lp[None], text, band=self.band, blank=self.blank, free_ends=self.free_ends)
+        ext = torch.full((2 * L + 1,), self.blank, dtype=torch.int64, device=dev)
+        ext[1::2] = text[0]
+        pos = res.path[0].long()
+        frame_logp = lp.gather(1, ext[pos].clamp(0, lp.shape[1] - 1)[:, None])[:, 0]
+        if self.free_ends:                               # the two end states emitted the best symbol's log-probability
+            frame_logp = torch.where((pos == 0) | (pos == 2 * L), lp.amax(-1), frame_logp)
+        table = utterance_cuts(res.path[0], frame_logp, cuts, L, self.conf_window, self.free_ends)
+        head = torch.stack([res.score[0], res.ok[0].double()])
+        flat = torch.cat([head, table.reshape(-1)]).cpu()                    # the one read-back
+        ok = bool(flat[1] != 0)
+        rows = flat[2:].reshape(-1, 5).tolist() if ok else []
+        utts = [{"start_s": r[0] * frame_seconds, "end_s": r[1] * frame_seconds, "frames": int(r[2]), "mean_logp": r[3],
+                 "min_window_logp": r[4]} for r in rows]
+        return {"ok": ok, "score": float(flat[0]), "frame_seconds": frame_seconds, "utterances": utts}
+
+
+def align_long_records(out, text_ids, cuts, decode: Callable[[torch.Tensor], str]) -> List[str]:
+    """The lines `start|end|confidence|text` for one LongAlignPipeline.align result (no newline): seconds with three decimals, the
+    confidence = min_window_logp (a log-probability per frame: nearer 0 is better), and `decode` (the caller's tokenizer.decode, ids
+    tensor -> str, as in align_records) on each utterance's labels."""
+    text = torch.as_tensor(text_ids, dtype=torch.int64).cpu().reshape(-1)
+    edges = list(cuts) + [text.numel()]
+    return [f"{u['start_s']:.3f}|{u['end_s']:.3f}|{u['min_window_logp']:.4f}|" + decode(text[edges[i]:edges[i + 1]])
+            for i, u in enumerate(out["utterances"])]
 
 
 class GraphedForward:
