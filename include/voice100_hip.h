@@ -803,6 +803,25 @@ long long v100_flac_workspace_bytes(int B, int S, int H, long long stage_ints);
 int v100_flac_decode(const unsigned char* bytes, long long nbytes, const int* table, void* ws, float* wave, int* pcm, int* lengths,
                      int* status, int B, int S, int H, long long stage_ints, int max_file_bytes, int Cw, int Cp, int Nmax, void* stream);
 
+/* ---- K30 FLAC encoding (csrc/flac_enc.hip): B items -> their FLAC frames, four launches and no read-back.
+ * Input: wave [R][C][N] fp32 (quantised as clamp(rint(x 2^(bits-1))), ties to even), or, when wave is NULL, pcm [R][C][N] int32;
+ * C 1 or 2, bits_per_sample 8, 16 or 24, N < 2^31.  ftab [F][8] int32 on the device, one row per frame, frames in file order and files
+ * in item order: {input row, first sample within the row, samples (1 .. block_size; only an item's last frame is shorter), frame
+ * number within the item, item, 0, 0, 0} -- items are segments of rows, so pieces of one long recording are encoded without a copy.
+ * 16 <= block_size <= 4608, max_lpc_order 0 .. 12 (0 = fixed predictors only), max_partition_order 0 .. 6.  rate_code / rate_extra:
+ * the frame header's sample-rate code (0 .. 11, 13, 14) and the 16-bit value that follows codes 13 and 14.
+ * ws: v100_flac_encode_workspace_bytes(F, C) bytes (-1 = unsupported).
+ * Outputs: out [out_bytes] uint8 (zeroed by the call; out_bytes a multiple of 4): the frames, contiguous, in ftab's order; the caller
+ * sizes it for the verbatim form, sum over frames of 18 + ceil((16 + (C bits + (C == 2)) samples) / 8), which no frame exceeds.
+ * report [F] int32 = each frame's bytes.  status [B][2] int32 = {0, 0} or {code, 0x7FFFFFFF - the item's first offending sample}:
+ * 1 a non-finite sample, 2 an int32 sample outside the width (both are encoded as 0 / clamped, the item is to be refused),
+ * 3 an internal inconsistency (the frame is left zero), 4 a frame-table row outside the input.
+ * 1 on a bad shape; 3 on a NULL pointer (one of wave and pcm may be NULL). */
+long long v100_flac_encode_workspace_bytes(int F, int C);
+int v100_flac_encode(const float* wave, const int* pcm, const int* ftab, void* ws, unsigned char* out, int* report, int* status,
+                     int B, int F, int R, int C, long long N, int bits_per_sample, int block_size, int max_lpc_order,
+                     int max_partition_order, int rate_code, int rate_extra, long long out_bytes, void* stream);
+
 /* ---- K19 WORLD feature statistics (csrc/world_stat.hip): one accumulation step of voice100/calc_stat.py:40-56 over a padded batch.
  * f0 [B][T], logspc [B][T][S], codeap [B][T][A] fp32, f0_len [B] int32, all on the device and contiguous (4-byte alignment is
  * enough).  Frame (b, t) is valid iff t < min(max(f0_len[b], 0), T).  The call ADDS to moments, float64 [4 + 2S + 2A]:

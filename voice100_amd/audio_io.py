@@ -11,6 +11,12 @@ native FLAC file (LibriSpeech's format; 8 to 24 bits, 1 to 8 channels), `load_au
 and `load_batch` takes either.  FLAC parity with libFLAC rests on the three worked examples of the format's RFC until real files
 exist under tests/golden/flac.  Out of scope: Ogg-FLAC, files with a leading ID3 tag, FLAC of unknown length, 32-bit FLAC and every
 lossy format.
+
+Writing: `save_wav` (PCM 8 / 16 / 24 bits, on the host, no GPU needed), `encode_flac` / `save_flac` (csrc/flac_enc.hip: the frames are
+searched, costed exactly and packed on the device, the host adds b'fLaC' and STREAMINFO), `save_audio` by extension and `save_batch` for
+a batch on the device.  Floats become integers as clamp(rint(x 2^(bits-1))), ties to even, in every writer.  Out of scope when writing:
+Ogg-FLAC, variable blocking, escape-coded partitions, more than two channels, 32-bit samples, metadata blocks other than STREAMINFO,
+dither and every lossy format.
 """
 import math
 import struct
@@ -292,8 +298,280 @@ def load_audio(path):
     raise ValueError(f"{path}: neither WAV nor FLAC (it begins {magic!r}; b'RIFF' and b'fLaC' are read)")
 
 
+# ---- writing: WAV on the host, FLAC frames on the device (csrc/flac_enc.hip) -----------------------------------------------------
+_FLAC_ENC_STATUS = {
+    1: "a non-finite sample (NaN or infinity) at sample {w}",
+    2: "an integer sample outside the {bits}-bit range at sample {w}",
+    3: "an internal inconsistency between the encoder's plan and its bit stream (a bug: please report the input)",
+    4: "a segment outside the input (near sample {w})",
+}
+_FLAC_RATE_CODES = {88200: 1, 176400: 2, 192000: 3, 8000: 4, 16000: 5, 22050: 6, 24000: 7, 32000: 8, 44100: 9, 48000: 10, 96000: 11}
+_FLAC_ENC_MAX_FRAMES = 1 << 24
+_FLAC_ENC_MAX_BYTES = 1 << 36
+
+
+def _check_format(who, sample_rate, bits_per_sample, channels):
+    if bits_per_sample not in (8, 16, 24):
+        raise ValueError(f"{who}: bits_per_sample must be 8, 16 or 24 (got {bits_per_sample!r})")
+    if channels not in (1, 2):
+        raise ValueError(f"{who}: 1 or 2 channels are written (got {channels})")
+    if isinstance(sample_rate, bool) or int(sample_rate) != sample_rate or not 1 <= int(sample_rate) <= 655350:
+        raise ValueError(f"{who}: sample_rate must be an integer in 1 .. 655350 (got {sample_rate!r})")
+
+
+def _flac_rate_code(rate):
+    """(frame-header code, 16-bit trailer): a table entry, else Hz, else tens of Hz, else 0 = "as STREAMINFO says"."""
+    if rate in _FLAC_RATE_CODES:
+        return _FLAC_RATE_CODES[rate], 0
+    if rate < 65536:
+        return 13, rate
+    if rate % 10 == 0 and rate // 10 < 65536:
+        return 14, rate // 10
+    return 0, 0
+
+
+def _flac_enc_plan(lengths, rows, starts, R, Nrow, C, bits_per_sample, block_size):
+    """The frame table v100_flac_encode takes (numpy, host only): (ftab [F][8] int32, first frame of every item [B + 1], out_bytes).
+    ValueError naming the item for a length of 0, of 2^31 or more, or past the end of its row, and for a batch beyond one call."""
+    B = len(lengths)
+    frames_total, bytes_total = 0, 0
+    for b in range(B):
+        n, r, s = int(lengths[b]), int(rows[b]), int(starts[b])
+        if n == 0:
+            raise ValueError(f"encode_flac: item {b} has length 0 (a FLAC total of 0 means 'unknown', which flac_info refuses)")
+        if n < 0 or n >= 2 ** 31:
+            raise ValueError(f"encode_flac: item {b} has {n} samples; 1 .. 2^31 - 1 are encoded")
+        if not 0 <= r < R or s < 0 or s + n > Nrow:
+            raise ValueError(f"encode_flac: item {b} (row {r}, samples {s} .. {s + n}) lies outside the input [{R}, {Nrow}]")
+        f = -(-n // block_size)
+        frames_total += f
+        bytes_total += 18 * f + (16 * f + (C * bits_per_sample + (C == 2)) * n + 7 * f) // 8
+        if frames_total > _FLAC_ENC_MAX_FRAMES or bytes_total > _FLAC_ENC_MAX_BYTES:
+            raise ValueError(f"encode_flac: the batch needs more frames or bytes than one call indexes (at item {b}: {frames_total} frames, "
+                             f"{bytes_total} bytes); encode fewer items per call")
+    lens = np.asarray(lengths, np.int64)
+    nf = -(-lens // block_size)
+    first = np.concatenate([[0], np.cumsum(nf)])
+    item = np.repeat(np.arange(B, dtype=np.int64), nf)
+    num = np.arange(int(first[-1]), dtype=np.int64) - first[item]
+    ftab = np.zeros((int(first[-1]), 8), np.int32)
+    ftab[:, 0] = np.asarray(rows, np.int64)[item]
+    ftab[:, 1] = np.asarray(starts, np.int64)[item] + num * block_size
+    ftab[:, 2] = np.minimum(block_size, lens[item] - num * block_size)
+    ftab[:, 3] = num
+    ftab[:, 4] = item
+    return ftab, first, -(-bytes_total // 16) * 16
+
+
+def _flac_streaminfo(rate, channels, bits, total, block_size, min_frame, max_frame, md5):
+    x = (rate << 44) | ((channels - 1) << 41) | ((bits - 1) << 36) | total
+    body = (block_size.to_bytes(2, "big") * 2 + min_frame.to_bytes(3, "big") + max_frame.to_bytes(3, "big") + x.to_bytes(8, "big") + md5)
+    return b"fLaC" + bytes([0x80]) + len(body).to_bytes(3, "big") + body
+
+
+def _quantise(x: torch.Tensor, bits: int) -> torch.Tensor:
+    """clamp(rint(x 2^(bits-1))), ties to even (the product is exact in float32), as int32; integer input passes through."""
+    if not x.dtype.is_floating_point:
+        return x.to(torch.int32)
+    return torch.clamp(torch.round(x.float() * float(1 << (bits - 1))), -float(1 << (bits - 1)), float((1 << (bits - 1)) - 1)).to(torch.int32)
+
+
+@torch.no_grad()
+def encode_flac(wave_or_pcm, lengths=None, sample_rate=16000, bits_per_sample=16, block_size=4096, max_lpc_order=8, max_partition_order=6,
+                md5=False, rows=None, starts=None):
+    """A batch of waveforms on the device -> a list of FLAC files as bytes, encoded on the GPU in one pass (csrc/flac_enc.hip).
+
+    wave_or_pcm: float32 [B, N] or [B, C, N] (C 1 or 2), quantised as clamp(rint(x 2^(bits-1))) with ties to even -- a wave that came
+    from a file of this width returns to its integers -- or int32 PCM of the same shapes.  Item b is samples
+    starts[b] .. starts[b] + lengths[b] of row rows[b] (defaults: row b, start 0, the whole row), so segments of one long recording
+    are encoded without a copy.  Fixed blocking (`block_size` 16 .. 4608, the last frame shorter); per frame and channel the cheapest,
+    by exact bit count, of constant, verbatim, fixed orders 0-4 and LPC orders 1 .. `max_lpc_order` (0 .. 12; 0 = none), each over Rice
+    parameters 0-14 and partition orders 0 .. `max_partition_order` (0 .. 6); stereo frames take the cheapest of independent, left/side,
+    side/right and mid/side.  The host writes b'fLaC' and STREAMINFO (block sizes = block_size, smallest and largest frame, rate,
+    channels, width, total samples, MD5) ahead of the device's frames.
+
+    Read-backs: TWO -- the frame sizes with the per-item status, then the bytes themselves -- plus one for `lengths` when that is a
+    device tensor.  `md5=True` adds a third: the integer PCM of every item is quantised on the device, copied to the host (4 bytes
+    per sample) and hashed there, which costs about as much as the rest of the call; `md5=False` writes the all-zero "unknown" signature.
+
+    ValueError naming the item for: a length of 0, 2^31 samples or more, a segment outside its row, a non-finite sample (with its
+    index), an integer sample outside the width, more than one call indexes; ValueError for an unsupported width, channel count,
+    rate or search setting.  RuntimeError without a GPU: there is no CPU fallback."""
+    x = wave_or_pcm
+    if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3) or x.dtype not in (torch.float32, torch.int32):
+        raise ValueError("encode_flac: a float32 or int32 tensor [B, N] or [B, C, N] is encoded")
+    C = 1 if x.dim() == 2 else x.shape[1]
+    _check_format("encode_flac", sample_rate, bits_per_sample, C)
+    if not 16 <= int(block_size) <= 4608 or not 0 <= int(max_lpc_order) <= 12 or not 0 <= int(max_partition_order) <= 6:
+        raise ValueError(f"encode_flac: block_size 16 .. 4608, max_lpc_order 0 .. 12 and max_partition_order 0 .. 6 are supported "
+                         f"(got {block_size}, {max_lpc_order}, {max_partition_order})")
+    R, Nmax = x.shape[0], x.shape[-1]
+    if R < 1 or Nmax >= 2 ** 31:
+        raise ValueError(f"encode_flac: input of shape {tuple(x.shape)}: at least one row and fewer than 2^31 samples per row are encoded")
+
+    def host_list(v):
+        if v is None:
+            return None
+        v = v.cpu().tolist() if isinstance(v, torch.Tensor) else [int(e) for e in v]
+        return [int(e) for e in v]
+    rows_l, starts_l, lens_l = host_list(rows), host_list(starts), host_list(lengths)
+    B = len(rows_l) if rows_l is not None else len(starts_l) if starts_l is not None else len(lens_l) if lens_l is not None else R
+    if rows_l is None:
+        if B != R:
+            raise ValueError(f"encode_flac: {B} items for {R} rows; pass `rows` to encode segments")
+        rows_l = list(range(R))
+    starts_l = [0] * B if starts_l is None else starts_l
+    lens_l = [Nmax - s for s in starts_l] if lens_l is None else lens_l
+    if not (len(rows_l) == len(starts_l) == len(lens_l) == B) or B < 1:
+        raise ValueError(f"encode_flac: rows, starts and lengths must have one entry per item ({len(rows_l)}, {len(starts_l)}, {len(lens_l)})")
+    ftab, first, out_bytes = _flac_enc_plan(lens_l, rows_l, starts_l, R, Nmax, C, int(bits_per_sample), int(block_size))
+    if not torch.cuda.is_available() or not x.is_cuda:
+        raise RuntimeError("encode_flac: voice100_amd runs on the GPU only (no CPU fallback): FLAC frames are encoded on the device"
+                           + ("" if not torch.cuda.is_available() else f" (got a tensor on {x.device})"))
+    F = ftab.shape[0]
+    rate = int(sample_rate)
+    code, extra = _flac_rate_code(rate)
+    x = x.contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    with torch.cuda.device(x.device):
+        ws_bytes = int(N.helper("v100_flac_encode_workspace_bytes", F, C))
+        if ws_bytes < 0:
+            raise ValueError(f"encode_flac: unsupported batch ({F} frames of {C} channels)")
+        d_ftab = torch.from_numpy(ftab).to(x.device)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=x.device)
+        out = torch.empty((out_bytes,), dtype=torch.uint8, device=x.device)
+        Fp = -(-F // 4) * 4
+        rep = torch.empty((Fp + 2 * B,), dtype=torch.int32, device=x.device)
+        is_float = x.dtype == torch.float32
+        N.call("v100_flac_encode", x if is_float else None, None if is_float else x, d_ftab, ws, out, rep[:Fp], rep[Fp:], B, F, R, C, Nmax,
+               int(bits_per_sample), int(block_size), int(max_lpc_order), int(max_partition_order), code, extra, out_bytes)
+        host = rep.cpu().numpy()                                       # read-back 1: frame sizes and status
+        sizes, st = host[:F].astype(np.int64), host[Fp:].reshape(B, 2)
+        for b in range(B):
+            if st[b, 0]:
+                where = 0x7FFFFFFF - int(st[b, 1])
+                raise ValueError(f"encode_flac: item {b}: " + _FLAC_ENC_STATUS.get(int(st[b, 0]), "status {c}").format(
+                    w=where, bits=bits_per_sample, c=int(st[b, 0])))
+        offs = np.concatenate([[0], np.cumsum(sizes)])
+        data = out[:int(offs[-1])].cpu().numpy().tobytes()             # read-back 2: the frames
+        sums = [bytes(16)] * B
+        if md5:
+            import hashlib
+            seg = torch.cat([x.reshape(R, C, Nmax)[r, :, s:s + n] for r, s, n in zip(rows_l, starts_l, lens_l)], dim=1)
+            pcm = _quantise(seg, int(bits_per_sample)).cpu().numpy()   # read-back 3: [C, all samples] int32
+            nb, at = bits_per_sample // 8, 0
+            for b, n in enumerate(lens_l):
+                inter = np.ascontiguousarray(pcm[:, at:at + n].T).reshape(-1)
+                sums[b] = hashlib.md5(np.ascontiguousarray(inter.astype("<i4").view(np.uint8).reshape(-1, 4)[:, :nb]).tobytes()).digest()
+                at += n
+    files = []
+    for b in range(B):
+        f0, f1 = int(first[b]), int(first[b + 1])
+        fs = sizes[f0:f1]
+        head = _flac_streaminfo(rate, C, int(bits_per_sample), lens_l[b], int(block_size), int(fs.min()), int(fs.max()), sums[b])
+        files.append(head + data[int(offs[f0]):int(offs[f1])])
+    return files
+
+
+def _pcm_bytes(waveform, bits_per_sample, who):
+    """[C, N] or [N] tensor (float: quantised like encode_flac; integer: taken as PCM) -> (interleaved little-endian bytes, C, N)."""
+    x = waveform.detach().cpu() if isinstance(waveform, torch.Tensor) else torch.as_tensor(waveform)
+    if x.dim() == 1:
+        x = x[None]
+    if x.dim() != 2:
+        raise ValueError(f"{who}: waveform must be [channels, samples] or [samples] (got {tuple(x.shape)})")
+    if x.dtype.is_floating_point and not bool(torch.isfinite(x).all()):
+        bad = int((~torch.isfinite(x)).nonzero()[0, 1])
+        raise ValueError(f"{who}: a non-finite sample (NaN or infinity) at sample {bad}")
+    q = _quantise(x, bits_per_sample).numpy().T                        # [N, C]
+    if bits_per_sample == 8:
+        raw = (q + 128).astype(np.uint8).tobytes()
+    elif bits_per_sample == 16:
+        raw = q.astype("<i2").tobytes()
+    else:
+        raw = np.ascontiguousarray(np.ascontiguousarray(q.astype("<i4")).view(np.uint8).reshape(-1, 4)[:, :3]).tobytes()
+    return raw, x.shape[0], x.shape[1]
+
+
+def save_wav(path, waveform, sample_rate, bits_per_sample=16):
+    """Write a PCM WAV file of 8 (unsigned), 16 or 24 bits: waveform [channels, samples] or [samples], on any device, float (quantised
+    as clamp(rint(x 2^(bits-1))), ties to even, the rule of encode_flac) or integer PCM.  Needs no GPU; `load_wav` returns the same
+    integers over 2^(bits-1).  ValueError for another width, a non-finite sample or an empty waveform."""
+    if bits_per_sample not in (8, 16, 24):
+        raise ValueError(f"save_wav: bits_per_sample must be 8, 16 or 24 (got {bits_per_sample!r})")
+    if isinstance(sample_rate, bool) or int(sample_rate) != sample_rate or not 1 <= int(sample_rate) < 2 ** 32:
+        raise ValueError(f"save_wav: sample_rate must be a positive integer (got {sample_rate!r})")
+    raw, C, n = _pcm_bytes(waveform, bits_per_sample, "save_wav")
+    if n < 1 or not 1 <= C < 65536 or len(raw) >= 2 ** 32 - 36:
+        raise ValueError(f"save_wav: {C} channels of {n} samples cannot be written as one WAV file")
+    width = bits_per_sample // 8
+    fmt = struct.pack("<HHIIHH", _PCM, C, int(sample_rate), int(sample_rate) * C * width, C * width, bits_per_sample)
+    with open(path, "wb") as f:
+        f.write(b"RIFF" + struct.pack("<I", 36 + len(raw) + (len(raw) & 1)) + b"WAVE" + b"fmt " + struct.pack("<I", 16) + fmt)
+        f.write(b"data" + struct.pack("<I", len(raw)) + raw + (b"\0" if len(raw) & 1 else b""))
+
+
+def save_flac(path, waveform, sample_rate, bits_per_sample=16, **enc):
+    """Write a FLAC file: waveform [channels, samples] or [samples] (float32 or int32; moved to the GPU if it is not there), encoded by
+    `encode_flac` (`enc`: block_size, max_lpc_order, max_partition_order, md5).  RuntimeError without a GPU."""
+    x = waveform[None] if waveform.dim() == 1 else waveform
+    if x.dim() != 2:
+        raise ValueError(f"save_flac: waveform must be [channels, samples] or [samples] (got {tuple(waveform.shape)})")
+    if not torch.cuda.is_available():
+        raise RuntimeError("save_flac: voice100_amd runs on the GPU only (no CPU fallback): FLAC frames are encoded on the device")
+    if not x.is_cuda:
+        x = x.to(torch.device("cuda", torch.cuda.current_device()))
+    data = encode_flac(x[None], None, sample_rate, bits_per_sample, **enc)[0]
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def _audio_kind(path, who):
+    ext = str(path).lower().rsplit(".", 1)[-1] if "." in str(path) else ""
+    if ext not in ("wav", "flac"):
+        raise ValueError(f"{who}: {path}: the file name must end in .wav or .flac")
+    return ext
+
+
+def save_audio(path, waveform, sample_rate, bits_per_sample=16, **enc):
+    """`save_wav` or `save_flac`, by the file name's extension (.wav / .flac); anything else is a ValueError naming the two."""
+    if _audio_kind(path, "save_audio") == "wav":
+        if enc:
+            raise ValueError(f"save_audio: {sorted(enc)} apply to .flac files only")
+        return save_wav(path, waveform, sample_rate, bits_per_sample)
+    return save_flac(path, waveform, sample_rate, bits_per_sample, **enc)
+
+
+def save_batch(paths, wave, lengths=None, sample_rate=16000, bits_per_sample=16, **enc):
+    """Write row b of wave [B, N] (or [B, C, N]) on the device, up to lengths[b], to paths[b] (.wav or .flac, mixed freely): ONE
+    `encode_flac` call for all .flac paths, ONE device-to-host copy for all .wav paths.  Nothing is written when a name has another
+    extension (ValueError) or an item is refused."""
+    paths = list(paths)
+    kinds = [_audio_kind(p, "save_batch") for p in paths]
+    if wave.dim() not in (2, 3) or wave.shape[0] != len(paths):
+        raise ValueError(f"save_batch: {len(paths)} paths for a wave of shape {tuple(wave.shape)}")
+    lens = [wave.shape[-1]] * len(paths) if lengths is None else [int(v) for v in (lengths.cpu().tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+    if len(lens) != len(paths):
+        raise ValueError(f"save_batch: {len(paths)} paths and {len(lens)} lengths")
+    for b, n in enumerate(lens):
+        if not 1 <= n <= wave.shape[-1]:
+            raise ValueError(f"save_batch: item {b} has length {n}; 1 .. {wave.shape[-1]} samples are written")
+    fl = [b for b, k in enumerate(kinds) if k == "flac"]
+    wv = [b for b, k in enumerate(kinds) if k == "wav"]
+    files = encode_flac(wave, [lens[b] for b in fl], sample_rate, bits_per_sample, rows=fl, **enc) if fl else []
+    host = wave[torch.tensor(wv, device=wave.device)][..., :max(lens[b] for b in wv)].cpu() if wv else None
+    for k, b in enumerate(wv):
+        _pcm_bytes(host[k][..., :lens[b]], bits_per_sample, f"save_batch: item {b}")      # refuses before anything is written
+    for b, data in zip(fl, files):
+        with open(paths[b], "wb") as f:
+            f.write(data)
+    for k, b in enumerate(wv):
+        save_wav(paths[b], host[k][..., :lens[b]], sample_rate, bits_per_sample)
+
+
 # ---- the filter bank --------------------------------------------------------------------------------------------------------
-ResampleKernel = namedtuple("ResampleKernel", "o n width L dense starts taps")
+ResampleKernel =namedtuple("ResampleKernel", "o n width L dense starts taps")
 ResampleKernel.__doc__ = """The polyphase bank of one rate pair, reduced to o / n: `dense` [n, 2 width + o] float32 (the table
 torchaudio convolves with), and the compact form the kernel takes -- `starts` [n] int32, `taps` [n, L] float32 with
 taps[p] = dense[p, starts[p]:starts[p] + L] (zero where that passes the end of the dense row), L = 2 width + 2."""

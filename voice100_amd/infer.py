@@ -19,7 +19,8 @@ import torch
 import torch.distributed as dist
 
 __all__ = ["shard_indices", "scatter_run", "TTSPipeline", "TTSPipelineV2", "ASRPipeline", "AlignPipeline", "align_records",
-           "ErrorRate", "GraphedForward", "window_plan", "windowed_logits", "utterance_cuts", "LongAlignPipeline", "align_long_records"]
+           "ErrorRate", "GraphedForward", "window_plan", "windowed_logits", "utterance_cuts", "LongAlignPipeline", "align_long_records",
+           "cut_utterances"]
 
 
 def shard_indices(n_items: int, rank: int, world: int, mode: str = "contiguous") -> torch.Tensor:
@@ -132,6 +133,16 @@ def _tts_evaluate(self, batches, meter=None):
     return meter.compute()
 
 
+def _tts_save(self, out, paths, bits_per_sample: int = 16, **enc):
+    """Write the synthesis of __call__ to files: out["wave"][b, :out["wave_len"][b]] at the vocoder's sample rate to paths[b] (.wav or
+    .flac, `audio_io.save_batch`: one FLAC encoding pass on the device, one copy for the WAV files).  ValueError when `out` holds no
+    "wave" (a pipeline built with synthesize=False or without a vocoder)."""
+    from .audio_io import save_batch
+    if "wave" not in out or "wave_len" not in out:
+        raise ValueError(f"{type(self).__name__}.save: the result holds no \"wave\" (synthesize=False, or no vocoder): nothing to write")
+    save_batch(paths, out["wave"], out["wave_len"], int(self.vocoder.sample_rate), bits_per_sample, **enc)
+
+
 class TTSPipeline:
     """BASELINE configs[2] end to end on the device (update_samples.py:46-84, the pyworld synthesis included):
 
@@ -161,7 +172,7 @@ class TTSPipeline:
     def __call__(self, text: torch.Tensor, text_len: torch.Tensor):
         return self._run(text, text_len, self.synthesize)[0]
 
-    score, evaluate = _tts_score, _tts_evaluate
+    score, evaluate, save = _tts_score, _tts_evaluate, _tts_save
 
     def _run(self, text: torch.Tensor, text_len: torch.Tensor, synthesize: bool):
         """The chain of __call__: its result, and the audio model's own features (mel-cepstra with a use_mcep vocoder)."""
@@ -218,7 +229,7 @@ class TTSPipelineV2:
     def __call__(self, text: torch.Tensor, text_len: torch.Tensor):
         return self._run(text, text_len, self.synthesize)[0]
 
-    score, evaluate = _tts_score, _tts_evaluate
+    score, evaluate, save = _tts_score, _tts_evaluate, _tts_save
 
     def _run(self, text: torch.Tensor, text_len: torch.Tensor, synthesize: bool):
         """The chain of __call__: its result, and the audio model's own features (mel-cepstra with a use_mcep vocoder)."""
@@ -645,6 +656,47 @@ class LongAlignPipeline:
         utts = [{"start_s": r[0] * frame_seconds, "end_s": r[1] * frame_seconds, "frames": int(r[2]), "mean_logp": r[3],
                  "min_window_logp": r[4]} for r in rows]
         return {"ok": ok, "score": float(flat[0]), "frame_seconds": frame_seconds, "utterances": utts}
+
+
+def cut_utterances(wave: torch.Tensor, sample_rate: int, out, paths, pad_s: float = 0.0, bits_per_sample: int = 16, **enc):
+    """Turn a `LongAlignPipeline.align` result into files: utterance u's samples [floor((start_s - pad_s) rate), ceil((end_s + pad_s) rate)),
+    clamped to the recording, go to paths[u] (.flac: all of them in ONE `encode_flac` call that reads the segments in place through
+    rows / starts; .wav: one copy of the recording to the host).  wave: the recording [samples] or [channels, samples] on the device.
+    Returns the sample ranges [(begin, end)].  Raises, and writes nothing, when the alignment failed (`ok` False), when the number
+    of paths differs from the number of utterances, or when an utterance is empty."""
+    import math
+    from . import audio_io as A
+    if not out.get("ok", False):
+        raise ValueError("cut_utterances: the alignment failed (ok is False): nothing is written")
+    utts, paths = out["utterances"], list(paths)
+    if len(paths) != len(utts):
+        raise ValueError(f"cut_utterances: {len(paths)} paths for {len(utts)} utterances")
+    if wave.dim() not in (1, 2):
+        raise ValueError(f"cut_utterances: the recording must be [samples] or [channels, samples] (got {tuple(wave.shape)})")
+    kinds = [A._audio_kind(p, "cut_utterances") for p in paths]
+    total = wave.shape[-1]
+    ranges = []
+    for u, ut in enumerate(utts):
+        a = min(max(math.floor((ut["start_s"] - pad_s) * sample_rate), 0), total)
+        e = min(max(math.ceil((ut["end_s"] + pad_s) * sample_rate), 0), total)
+        if e <= a:
+            raise ValueError(f"cut_utterances: utterance {u} ({ut['start_s']:.3f} s .. {ut['end_s']:.3f} s) holds no samples")
+        ranges.append((a, e))
+    fl = [u for u, k in enumerate(kinds) if k == "flac"]
+    if fl:
+        rec = wave[None] if wave.dim() == 2 else wave[None, None]
+        files = A.encode_flac(rec, [ranges[u][1] - ranges[u][0] for u in fl], sample_rate, bits_per_sample, rows=[0] * len(fl),
+                              starts=[ranges[u][0] for u in fl], **enc)
+    host = wave.cpu() if len(fl) < len(paths) else None
+    if host is not None:
+        A._pcm_bytes(host, bits_per_sample, "cut_utterances")          # refuses a non-finite sample before anything is written
+    for u, data in zip(fl, files if fl else []):
+        with open(paths[u], "wb") as f:
+            f.write(data)
+    for u, k in enumerate(kinds):
+        if k == "wav":
+            A.save_wav(paths[u], host[..., ranges[u][0]:ranges[u][1]], sample_rate, bits_per_sample)
+    return ranges
 
 
 def align_long_records(out, text_ids, cuts, decode: Callable[[torch.Tensor], str]) -> List[str]:
