@@ -546,6 +546,27 @@ long long v100_ctc_align_long_workspace_bytes(int B, int T, int Lmax, int band);
 int v100_ctc_align_long_block(void);
 int v100_ctc_align_long(const float* logp, const long long* labels, const int* in_len, const int* lab_len, const float* free_logp, void* ws,
                         double* score, int* ok, int* path, int* align, int B, int T, int V, int Lmax, int band, int blank, void* stream);
+/* K31, the CTC pause cutter (csrc/cut_points.hip): where to cut recordings of up to 2^20 frames into pieces of at most max_frames
+ * frames for a batched decode.  logits [B][T][V] fp32, lengths [B] or NULL (clamped to [0, T] on the device; nothing beyond a row's
+ * length is read).  The rule, which tests/_cut_points_ref.py defines and the device equals exactly: a frame is silent where
+ * logits[blank] - max of the others (one fp32 subtraction; NaN is not silent) exceeds margin; the recording is trimmed to its non-silent
+ * frames; every silent run of min_gap frames or more is a cut (min_gap 0: none); what lies between cuts and is longer than
+ * C = max_frames - 2 pad is split left to right at its longest silent run that leaves min_frames on both sides and at most C on the
+ * left (ties to the latest), or, where there is none, forced at the first maximum of the margin in the second half of the reach.
+ * v100_ctc_cut_points fills the workspace and n_seg [B] int32, the number of pieces per row: two launches, nothing is read back.
+ * v100_ctc_cut_points_table, called with S >= 1 and the same T and pad, then writes start, end, forced [B][S] int32 from the workspace:
+ * the pieces widened by min(pad, half the silence shared with a neighbour), by min(pad, what is there) at the recording's two ends and
+ * not at all on a forced side; forced = 1 on the piece that begins at a forced cut; zeros beyond n_seg (and pieces beyond S are left
+ * out).  ws: v100_ctc_cut_points_workspace_bytes(B, T) bytes (0 = unsupported).  B >= 1, 1 <= T <= 2^20, 2 <= V <= 128,
+ * 0 <= blank < V, 2 <= max_frames <= 4096, pad >= 0, min_frames >= 1, max_frames - 2 pad >= 2 min_frames, min_gap >= 0, margin not NaN,
+ * 1 <= S <= T, else 1; a NULL pointer 3; both before anything touches a device.  v100_ctc_cut_points_span() / _pass(): frames per
+ * thread and per pass of the run scan (lengths around them and their multiples are the kernel's seams). */
+long long v100_ctc_cut_points_workspace_bytes(int B, int T);
+int v100_ctc_cut_points_span(void);
+int v100_ctc_cut_points_pass(void);
+int v100_ctc_cut_points(const float* logits, const int* lengths, void* ws, int* n_seg, int B, int T, int V, int blank, int max_frames,
+                        int min_gap, float margin, int pad, int min_frames, void* stream);
+int v100_ctc_cut_points_table(const void* ws, int* start, int* end, int* forced, int B, int T, int S, int pad, void* stream);
 /* K23, batched edit distance (csrc/edit_distance.hip): the Levenshtein distance (unit costs for substitution, insertion and
  * deletion) between hyp [B][Th] int64 and ref [B][Tr] int64, rows of hyp_len / ref_len [B] int32 ids (clamped to [0, width] on the
  * device; nothing beyond a row's length is read; ids compare on all 64 bits).  levels: 1 = id level (a token is one id), 2 = word

@@ -7,7 +7,8 @@ ids against reference ids (character / phone and word error counts) without leav
 the CTC prefix beam search, n best transcripts with their total log probabilities, where the reference decodes greedily, nor its
 fused form (K25): the same search with an lm.NGramLM voting inside every frame's selection, nor ctc_segment (K26): the CTC
 forward-backward over the alignments of a given transcript, reduced to time boundaries, durations and confidences per label and word,
-nor ctc_align_long (K29): the banded Viterbi that aligns a chapter-length recording to its text."""
+nor ctc_align_long (K29): the banded Viterbi that aligns a chapter-length recording to its text, nor ctc_cut_points (K31): where to
+cut a recording of any length, at its pauses, into pieces that the beam search and ctc_segment take."""
 import math
 from typing import NamedTuple, Optional
 
@@ -132,6 +133,65 @@ def ctc_align_long(log_probs: torch.Tensor, labels: torch.Tensor, input_lengths=
     if width == 0:
         align = align[:, :1]
     return CTCLongAlign(score, ok, path, align)
+
+
+class CutPoints(NamedTuple):
+    """What ctc_cut_points returns: S is the largest number of segments over the batch."""
+    start: torch.Tensor                                  # [B, S] int32: first frame of each segment, ascending, 0 beyond n_seg
+    end: torch.Tensor                                    # [B, S] int32: one past its last frame
+    forced: torch.Tensor                                 # [B, S] int32: 1 where the segment begins at a forced cut (no pause there)
+    n_seg: torch.Tensor                                  # [B] int32
+
+
+def ctc_cut_points(logits: torch.Tensor, lengths: torch.Tensor = None, blank: int = 0, max_frames: int = 3000, min_gap=25,
+                   margin: float = 0.0, pad: int = 5, min_frames: int = 50) -> CutPoints:
+    """Where to cut long recordings into pieces that fit ctc_beam_search and ctc_segment (K31, csrc/cut_points.hip): logits [B, T, V]
+    fp32 (the model's output), lengths [B] or None -> CutPoints(start, end, forced, n_seg) of device tensors.  One read-back, of
+    n_seg.max(), sizes S.
+
+    A frame is silent where logits[blank] - max of the others (one fp32 subtraction; NaN is not silent) exceeds `margin`; with
+    margin >= 0 its argmax is the blank, and CTC never merges labels across a blank, so the greedy decode of the pieces, concatenated,
+    is the greedy decode of the recording wherever no cut is forced.  The recording is trimmed to its non-silent frames (none:
+    n_seg = 0); every silent run of min_gap frames or more is a cut (min_gap=None: none, only the splitting below); what lies between
+    two cuts and is longer than C = max_frames - 2 pad is split left to right at its longest silent run that leaves min_frames
+    frames on both sides and at most C on the left (ties to the latest) or, where there is none, at the first maximum of the margin
+    over [a + max(C // 2, min_frames), min(a + C, b - min_frames)]: a forced cut, forced = 1 on the segment that begins there.
+    Segments are then widened into the silence around them: by min(pad, half of what they share with a neighbour), by
+    min(pad, what is there) at the recording's two ends, not at all on a forced side.  So segments are ascending, disjoint,
+    non-empty, at most max_frames long, inside each row's length, and every non-silent frame lies in exactly one.
+    tests/_cut_points_ref.py is the rule in numpy; the device equals it exactly, and two calls give equal bits.
+    Limits: 1 <= T <= 2^20, 2 <= V <= 128, 0 <= blank < V, 2 <= max_frames <= 4096, pad >= 0, min_frames >= 1,
+    max_frames - 2 pad >= 2 min_frames, min_gap >= 1 or None.  Lengths are clamped to [0, T]; nothing beyond a row's length is read."""
+    given = [t for t in (logits, lengths) if t is not None]
+    if not all(isinstance(t, torch.Tensor) for t in given) or logits is None:
+        raise RuntimeError("ctc_cut_points: GPU tensors only")
+    if logits.dim() != 3:
+        raise RuntimeError(f"ctc_cut_points: logits must be [B, T, V], got {list(logits.shape)}")
+    B, T, V = logits.shape                               # (the limits need no device: they are checked first)
+    blank, max_frames, pad, min_frames, margin = int(blank), int(max_frames), int(pad), int(min_frames), float(margin)
+    gap = 0 if min_gap is None else int(min_gap)
+    nbytes = N.helper("v100_ctc_cut_points_workspace_bytes", B, T) if B >= 1 else 0
+    if (nbytes <= 0 or not 2 <= V <= 128 or not 0 <= blank < V or not 2 <= max_frames <= 4096 or pad < 0 or min_frames < 1
+            or max_frames - 2 * pad < 2 * min_frames or (min_gap is not None and gap < 1) or math.isnan(margin)):
+        raise RuntimeError(f"ctc_cut_points: unsupported shape or argument (B = {B} >= 1, 1 <= T = {T} <= 2^20, 2 <= V = {V} <= 128, "
+                           f"0 <= blank = {blank} < V, 2 <= max_frames = {max_frames} <= 4096, pad = {pad} >= 0, min_frames = {min_frames} "
+                           f">= 1, max_frames - 2 pad >= 2 min_frames, min_gap = {min_gap} >= 1 or None and a margin that is not NaN are "
+                           "the limits)")
+    if lengths is not None and lengths.numel() != B:
+        raise RuntimeError(f"ctc_cut_points: lengths must have {B} elements")
+    if not all(t.is_cuda for t in given):
+        raise RuntimeError("ctc_cut_points: GPU tensors only")
+    logits = logits.contiguous().float()
+    dev = logits.device
+    lens = lengths.to(device=dev, dtype=torch.int32).contiguous() if lengths is not None else None
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    n_seg = torch.empty((B,), dtype=torch.int32, device=dev)
+    N.call("v100_ctc_cut_points", logits, lens, ws, n_seg, B, T, V, blank, max_frames, gap, margin, pad, min_frames)
+    S = int(n_seg.max())                                 # the one read-back: the tables are exactly that wide
+    start, end, forced = (torch.empty((B, S), dtype=torch.int32, device=dev) for _ in range(3))
+    if S > 0:
+        N.call("v100_ctc_cut_points_table", ws, start, end, forced, B, T, S, pad)
+    return CutPoints(start, end, forced, n_seg)
 
 
 def align_expand(text: torch.Tensor, align: torch.Tensor, text_len=None, head: int = 5, tail: int = 5):

@@ -20,7 +20,7 @@ import torch.distributed as dist
 
 __all__ = ["shard_indices", "scatter_run", "TTSPipeline", "TTSPipelineV2", "ASRPipeline", "AlignPipeline", "align_records",
            "ErrorRate", "GraphedForward", "window_plan", "windowed_logits", "utterance_cuts", "LongAlignPipeline", "align_long_records",
-           "cut_utterances"]
+           "cut_utterances", "batch_plan", "join_ids", "LongASRPipeline", "long_transcript_records"]
 
 
 def shard_indices(n_items: int, rank: int, world: int, mode: str = "contiguous") -> torch.Tensor:
@@ -707,6 +707,195 @@ def align_long_records(out, text_ids, cuts, decode: Callable[[torch.Tensor], str
     edges = list(cuts) + [text.numel()]
     return [f"{u['start_s']:.3f}|{u['end_s']:.3f}|{u['min_window_logp']:.4f}|" + decode(text[edges[i]:edges[i + 1]])
             for i, u in enumerate(out["utterances"])]
+
+
+def batch_plan(n_segments: int, max_batch: int):
+    """How LongASRPipeline packs its segments, sorted by length (longest first), into decode calls: [(lo, hi)] over the sorted order,
+    at most max_batch rows each, every segment exactly once.  The first row of a call is its longest: the call is padded to it."""
+    if n_segments < 0 or max_batch < 1:
+        raise ValueError("batch_plan: n_segments >= 0 and max_batch >= 1 are required")
+    return [(lo, min(lo + max_batch, n_segments)) for lo in range(0, n_segments, max_batch)]
+
+
+def join_ids(rows, sep):
+    """The ids of a whole transcript from its utterances' (lists of ints): the utterances in order, with the separator id between two
+    of them wherever neither supplies one (the one before does not end with it and the one after does not begin with it); empty
+    utterances are left out.  sep=None: plain concatenation."""
+    out = []
+    for row in rows:
+        row = [int(i) for i in row]
+        if not row:
+            continue
+        if out and sep is not None and out[-1] != sep and row[0] != sep:
+            out.append(int(sep))
+        out.extend(row)
+    return out
+
+
+class LongASRPipeline:
+    """A chapter-length recording -> its transcript as utterances with times, on the device:
+
+        path or waveform
+          -> audio_io.load_batch, mel                      feats [M, audio_size]
+          -> windowed_logits                               logits [T', V] from batched forwards over equal windows
+          -> decode.ctc_cut_points                         where to cut: at the pauses, pieces of at most max_frames frames  (K31)
+          -> gather                                        the segments sorted by length, at most max_batch rows per call, each call
+                                                           padded to its longest (stock indexing ops)
+          -> the decode of an ASRPipeline                  greedy, the prefix beam search, or the beam search with the LM   (K24, K25)
+          -> decode.ctc_segment (timed, or greedy)         times and confidences of the labels and words of each segment     (K26)
+          -> offsets                                       every frame index moves by its segment's start
+
+    The beam search and ctc_segment stop at 4096 frames and run one workgroup per row, so a recording is decoded as a batch of its
+    pieces.  Cutting inside a run of blank frames costs the greedy decode nothing (CTC never merges labels across a blank: the
+    pieces' decodes, concatenated, are the recording's); the beam search loses only what it would have carried across the pause,
+    and THE LANGUAGE MODEL'S CONTEXT RESTARTS AT EVERY CUT: each segment is scored as a sentence of its own.  A forced cut (a
+    stretch of max_frames frames without an admissible pause) may split a word; its segment says so in "forced".
+    An ASRPipeline is held and called for the decode; blank must be 0, as there.  Eval mode only, like windowed_logits.
+    Device-to-host copies: the number of segments S, one copy of the calls' widths, and the longest hypothesis of each call."""
+
+    def __init__(self, model, mel=None, beam_size=None, lm=None, lm_weight=0.5, length_bonus=0.0, keep=1500, max_frames=3000, min_gap=25,
+                 margin=0.0, pad=5, min_frames=50, max_batch=32, blank=0, sep=1, frame_seconds=None):
+        if int(blank) != 0:
+            raise RuntimeError(f"LongASRPipeline: blank = {blank}; the decode of ASRPipeline takes the blank at id 0")
+        if int(max_batch) < 1:
+            raise RuntimeError(f"LongASRPipeline: max_batch = {max_batch} must be at least 1")
+        self.asr = ASRPipeline(model, mel, beam_size=beam_size, nbest=1, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
+                               frame_seconds=frame_seconds)
+        self.model, self.mel = model, mel
+        self.keep, self.max_batch, self.blank, self.sep = int(keep), int(max_batch), int(blank), sep
+        self.cut = dict(max_frames=int(max_frames), min_gap=min_gap, margin=float(margin), pad=int(pad), min_frames=int(min_frames))
+
+    def _wave(self, path_or_wave, who):
+        if self.mel is None:
+            raise RuntimeError(f"LongASRPipeline.{who}: the pipeline has no mel transform to turn a waveform into features (pass feats= "
+                               "or logits=)")
+        if isinstance(path_or_wave, torch.Tensor):
+            return path_or_wave.to(self.mel.dft_basis.device).reshape(-1)
+        from .audio_io import load_batch
+        return load_batch([path_or_wave], self.mel.sample_rate, self.mel.dft_basis.device)[0][0]
+
+    def _frame_seconds(self):
+        if self.asr.frame_seconds is None and self.mel is None:
+            return None
+        return self.asr._frame_seconds("segments")
+
+    @torch.no_grad()
+    def segments(self, path_or_wave=None, feats: torch.Tensor = None, logits: torch.Tensor = None, timed: bool = True):
+        """path_or_wave: a WAV / FLAC file or a waveform [N] at the mel's sample rate; or feats [M, audio_size]; or logits [T', V]
+        that are already there.  Returns a dict of device tensors, segments in the recording's order: "seg_start", "seg_end", "forced" [S]
+        int32 (decode.ctc_cut_points); "ids" [S, L] int64 zero padded and "ids_len" [S] int32, L the longest hypothesis; "score" [S]
+        fp32: the beam search's score (the fused one with a language model), or for the greedy decode ctc_segment's log_prob; with
+        timed=True (or the greedy decode) the fields of decode.CTCSegments, [S, ...], whose frame fields ("start", "end",
+        "word_start", "word_end") are moved by seg_start inside each row's labels / words, so they count the recording's frames;
+        and "frame_seconds" (a float, or None where the pipeline has neither a mel nor frame_seconds)."""
+        from .decode import ctc_cut_points, ctc_segment
+        if logits is None:
+            if feats is None:
+                feats = self.mel(self._wave(path_or_wave, "segments").reshape(1, -1))[0]
+            logits = windowed_logits(self.model, feats, self.keep)
+        if not logits.is_cuda:
+            raise RuntimeError("LongASRPipeline.segments: GPU tensors only")
+        if logits.dim() != 2:
+            raise RuntimeError(f"LongASRPipeline.segments: logits must be [T', V], got {list(logits.shape)}")
+        logits = logits.contiguous().float()
+        dev = logits.device
+        T = logits.shape[0]
+        cp = ctc_cut_points(logits[None], None, self.blank, **self.cut)
+        seg_start, seg_end, forced = cp.start[0], cp.end[0], cp.forced[0]
+        S = seg_start.shape[0]                               # (ctc_cut_points read it back)
+        out = {"seg_start": seg_start, "seg_end": seg_end, "forced": forced}
+        greedy = self.asr.beam_size is None
+        with_seg = timed or greedy
+        seg_len = seg_end - seg_start
+        order = torch.argsort(seg_len, descending=True, stable=True)
+        plan = batch_plan(S, self.max_batch)
+        widths = seg_len[order][::self.max_batch].cpu().tolist() if S else []       # the longest of each call, one copy
+        parts = []
+        for (lo, hi), width in zip(plan, widths):
+            rows = order[lo:hi]
+            st, ln = seg_start[rows].long(), seg_len[rows].contiguous()
+            idx = (st[:, None] + torch.arange(width, device=dev)[None]).clamp_max(T - 1)
+            x = logits[idx]                                   # [rows, width, V]; what lies beyond a row's length is never read
+            if greedy:
+                ids, n = self.asr._best(x, ln)
+                score = None
+            else:
+                ids, n, score = self.asr._beam(x, ln, 1)[:3]
+                ids, n, score = ids[:, 0], n[:, 0].contiguous(), score[:, 0]
+            L = max(int(n.max()), 1)
+            ids = ids[:, :L].contiguous()
+            seg = ctc_segment(x, ln, ids, n, blank=self.blank, sep=self.sep) if with_seg else None
+            parts.append((rows, st, ids, n, score if score is not None else seg.log_prob, seg, L))
+        L = max([p[6] for p in parts], default=1)
+        ids_all = torch.zeros((S, L), dtype=torch.int64, device=dev)
+        n_all = torch.zeros((S,), dtype=torch.int32, device=dev)
+        score_all = torch.zeros((S,), dtype=torch.float32, device=dev)
+        fields = {}
+        if with_seg:
+            NW = (L + 1) // 2
+            wide = {"start": torch.int32, "end": torch.int32, "duration": torch.float32, "log_confidence": torch.float32}
+            words = {"word_first": torch.int32, "word_count": torch.int32, "word_start": torch.int32, "word_end": torch.int32,
+                     "word_log_confidence": torch.float32} if self.sep is not None else {}
+            fields = {k: torch.zeros((S, L), dtype=dt, device=dev) for k, dt in wide.items()}
+            fields.update({k: torch.zeros((S, NW), dtype=dt, device=dev) for k, dt in words.items()})
+            fields["log_prob"] = torch.zeros((S,), dtype=torch.float32, device=dev)
+            fields["n_words"] = torch.zeros((S,), dtype=torch.int32, device=dev) if self.sep is not None else None
+            for k in ("word_first", "word_count", "word_start", "word_end", "word_log_confidence"):
+                fields.setdefault(k, None)
+        for rows, st, ids, n, score, seg, Lc in parts:
+            ids_all[rows, :Lc] = ids
+            n_all[rows] = n
+            score_all[rows] = score
+            if seg is None:
+                continue
+            shift = st.int()[:, None]
+            in_labels = torch.arange(Lc, device=dev)[None] < n[:, None]
+            for k, v in seg._asdict().items():
+                if v is None:
+                    continue
+                if k in ("start", "end"):
+                    v = torch.where(in_labels, v + shift, v)
+                elif k in ("word_start", "word_end"):
+                    v = torch.where(torch.arange(v.shape[1], device=dev)[None] < seg.n_words[:, None], v + shift, v)
+                if v.dim() == 1:
+                    fields[k][rows] = v
+                else:
+                    fields[k][rows, :v.shape[1]] = v
+        out.update({"ids": ids_all, "ids_len": n_all, "score": score_all})
+        out.update(fields)
+        out["frame_seconds"] = self._frame_seconds()
+        return out
+
+    def transcribe(self, path, decode: Callable[[torch.Tensor], str]):
+        """A WAV / FLAC file -> {"text", "utterances": [{"start_s", "end_s", "text", "score", "forced", "words": [{"word", "start",
+        "end", "confidence"}]}], "frame_seconds"}, following ASRPipeline.transcribe_timed: times in seconds, an end cut at the file's
+        own duration, confidence = exp(word_log_confidence), `decode` the caller's tokenizer.decode (ids tensor -> str).  "text" is
+        the decode of all utterances' ids, joined by the separator id wherever neither neighbour supplies one (join_ids).  Needs a
+        `mel` and a separator id; one device-to-host copy per tensor."""
+        if self.sep is None:
+            raise RuntimeError("LongASRPipeline.transcribe: words need a separator id (segments() gives the label level)")
+        wave = self._wave(path, "transcribe")
+        out = self.segments(wave)
+        fs = out["frame_seconds"]
+        seconds = wave.shape[0] / self.mel.sample_rate
+        keys = ("seg_start", "seg_end", "forced", "ids", "ids_len", "score", "word_first", "word_count", "word_start", "word_end",
+                "word_log_confidence", "n_words")
+        s0, s1, forced, ids, n, score, first, count, start, end, conf, nw = (out[k].cpu() for k in keys)
+        conf = torch.exp(conf)
+        utts = []
+        for i in range(ids.shape[0]):
+            words = [{"word": decode(ids[i, int(first[i, w]):int(first[i, w]) + int(count[i, w])]), "start": int(start[i, w]) * fs,
+                      "end": min(int(end[i, w]) * fs, seconds), "confidence": float(conf[i, w])} for w in range(int(nw[i]))]
+            utts.append({"start_s": int(s0[i]) * fs, "end_s": min(int(s1[i]) * fs, seconds), "text": decode(ids[i, :int(n[i])]),
+                         "score": float(score[i]), "forced": bool(forced[i]), "words": words})
+        whole = join_ids([ids[i, :int(n[i])].tolist() for i in range(ids.shape[0])], self.sep)
+        return {"text": decode(torch.tensor(whole, dtype=torch.int64)), "utterances": utts, "frame_seconds": fs}
+
+
+def long_transcript_records(result) -> List[str]:
+    """The lines `start|end|score|text` for one LongASRPipeline.transcribe result (no newline): seconds with three decimals and the
+    utterance's score (a log-probability) with four, like align_long_records."""
+    return [f"{u['start_s']:.3f}|{u['end_s']:.3f}|{u['score']:.4f}|{u['text']}" for u in result["utterances"]]
 
 
 class GraphedForward:
