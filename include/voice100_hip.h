@@ -609,6 +609,39 @@ int v100_ctc_beam_search_lm(const float* logits, const int* lens, void* ws, long
                             const float* lm_logp, const int* lm_next, const float* lm_final, int S, int start_state, float alpha,
                             float beta, int use_eos, float* ctc_scores, float* lm_scores, int B, int T, int V, int W, int nbest,
                             int blank, void* stream);
+/* K32, the same search without a frame limit (the resumable form of csrc/beam.hip): the beam survives between launches, so logits
+ * can be pushed chunk by chunk, and any split into chunks gives the bits of one call over all the frames.  The caller owns two
+ * buffers and ZEROES BOTH ONCE, when the stream is created; the library never zeroes them:
+ *   ws:    v100_ctc_beam_stream_workspace_bytes(B, max_frames, V, W) bytes = B x (8 P + 4 ((1 + W max_frames + 3) & ~3)), P the
+ *          power of two >= max(64, 2 W max_frames): per row the child table and the trie's nodes for max_frames frames.  The
+ *          table's size enters the hash, so the capacity is fixed for the life of the stream; 20 to 36 bytes x W x max_frames a row;
+ *   state: v100_ctc_beam_stream_state_bytes(B, W) bytes = B x ((32 + 40 W + 15) & ~15): per row {started, nbeam, frames, 0} int32,
+ *          {offset, lmoff} fp64, then pb, pnb, tot fp32, node, par, last, len, state int32, lm, bias fp32, W of each, in beam order.
+ * Both helpers are host-only and return -1 on an unsupported shape.
+ * push: logits [B][T][V] fp32 and lens [B] int32 or NULL as K24's, 1 <= T <= 4096: row b runs clamp(lens[b], 0, T) more frames,
+ *   and never more than max_frames in all (the device clamps; the caller should count).  A row without frames keeps its state bit
+ *   for bit.  The LM form takes K25's tables and weights; they must be the same in every push of a stream.
+ * read: the current n best, outputs as K24's / K25's with ids [B][nbest][width]; a hypothesis' length is clamped to
+ *   min(the row's frames so far, width).  It runs no frame and stores nothing, so it may be called at any time, and twice.  The LM
+ *   form adds alpha lm_final[state] before the ranking iff `final`, exactly as K25's last ranking does with use_eos.  Reading the
+ *   labels back costs one dependent load per label of each hypothesis.
+ * Everything that comes out of `state` is clamped on the device before it is used as an index: a damaged state gives wrong text,
+ * never an access outside the row's buffers.
+ * B >= 1, 2 <= V <= 128, 1 <= W <= 64, max_frames >= 1 with W max_frames < 2^25 (the trie's keys stay below 2^32), 0 <= blank < V,
+ * 1 <= nbest <= W, width >= 1 and K25's limits on the LM, else 1; a NULL pointer (lens excepted) 3; both before anything touches a
+ * device. */
+long long v100_ctc_beam_stream_workspace_bytes(int B, int max_frames, int V, int W);
+long long v100_ctc_beam_stream_state_bytes(int B, int W);
+int v100_ctc_beam_stream_push(const float* logits, const int* lens, void* ws, void* state, int B, int T, int max_frames, int V, int W,
+                              int blank, void* stream);
+int v100_ctc_beam_stream_push_lm(const float* logits, const int* lens, void* ws, void* state, const float* lm_logp, const int* lm_next,
+                                 const float* lm_final, int S, int start_state, float alpha, float beta, int B, int T, int max_frames,
+                                 int V, int W, int blank, void* stream);
+int v100_ctc_beam_stream_read(const void* ws, const void* state, long long* ids, int* ids_len, float* scores, int B, int max_frames,
+                              int V, int W, int nbest, int width, void* stream);
+int v100_ctc_beam_stream_read_lm(const void* ws, const void* state, long long* ids, int* ids_len, float* scores, const float* lm_final,
+                                 int S, int start_state, float alpha, float beta, int final, float* ctc_scores, float* lm_scores, int B,
+                                 int max_frames, int V, int W, int nbest, int width, void* stream);
 /* K26, word timestamps and confidences (csrc/ctc_segment.hip): the CTC forward-backward over all alignments of a GIVEN transcript
  * in one launch, reduced per label and per word.  It is the posterior of the alignments given the transcript, not a posterior of
  * the transcript being right.  logits [B][T][V] fp32 (the kernel takes the log-softmax itself), labels [B][Lmax] int64; in_len /

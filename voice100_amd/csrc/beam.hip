@@ -43,6 +43,17 @@
 // extension's as the same sum.  The LM part is rescaled like the scores: lm is kept less that of the entry with the highest key,
 // the amount goes into an fp64 offset, and the length enters as a difference from that entry's.  The CTC recurrences never see the
 // LM.  ctc_beam_kernel<false> is K24, instruction for instruction.
+//
+// K32: the resumable form, ctc_beam_kernel<LM, true>.  Everything a frame needs from the past is the beam (in LDS), the two fp64
+// offsets and the trie, so a launch that loads the first two from a per-row state in global memory, runs a chunk of frames and
+// stores them again does the floating-point operations of the one-call form in its order: any split of a recording into chunks
+// gives the one call's bits.  What differs: the trie is the caller's for the life of the stream, zeroed once and sized for a
+// capacity in frames (the table's size enters the hash, so every launch uses all of it); a fresh node's number comes from the
+// row's absolute frame index; a row without frames in a chunk stores nothing.  Reading the n best is a mode of the same kernel,
+// without frames and without a store; the walk through the parent pointers is one dependent load per label of each hypothesis.
+// Every index and count that comes out of the state is clamped where it is loaded, so a damaged state gives wrong text and stays
+// inside the row's buffers.  ctc_beam_kernel<LM, false> is K24 / K25, instruction for instruction (the ISA of both was compared
+// with the parent's: the symbol's second template argument and an unread trailing kernel argument are the difference).
 #include "common.h"
 #include <math.h>
 
@@ -116,11 +127,24 @@ struct BmLm {
     float alpha, beta;
 };
 
-template <bool LM>
+// K32: what the resumable form (STREAM = true) takes beside that; the one-call forms never read it.  The beam of row b lives in
+// state + b * stride between two launches (bm_state_bytes): {started, nbeam, frames, 0} int32, {offset, lmoff} fp64, then per entry,
+// in beam order, pb, pnb, tot fp32, node, par, last, len, state int32, lm, bias fp32, W of each.
+struct BmStream {
+    unsigned char* state;
+    long long stride;                                   // bytes per row
+    int cap;                                            // the capacity in frames that the workspace was sized for
+    int width;                                          // read: the width of an ids row
+    int read;                                           // 0: run the frames and store the beam; 1: report the n best, store nothing
+};
+#define BM_STATE_HEAD 32
+#define BM_STATE_FIELDS 10
+
+template <bool LM, bool STREAM>
 __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __restrict__ logits, const int* __restrict__ lens,
                                                               unsigned char* ws, long long* __restrict__ ids, int* __restrict__ ids_len,
                                                               float* __restrict__ scores, int T, int V, int W, int nbest, int blank,
-                                                              long long region, int P, unsigned vmagic, BmLm lm) {
+                                                              long long region, int P, unsigned vmagic, BmLm lm, BmStream st) {
     __shared__ float s_score[BM_WMAX * BM_VMAX];        // candidate k V + c: total log probability
     __shared__ float s_lp[2][BM_VMAX];                  // frame t in s_lp[t & 1]: written one frame ahead
     __shared__ unsigned s_hist[4][256];                 // one histogram per radix pass
@@ -139,19 +163,51 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int n = lens ? lens[b] : T;
     n = __builtin_amdgcn_readfirstlane(min(max(n, 0), T));
+    // K32: the row's stored beam.  Everything read from it is clamped before it is used as an index or a count.
+    unsigned char* mine_st = nullptr;
+    int started = 0, t0 = 0;                            // t0: this row's frames before this launch
+    if constexpr (STREAM) {
+        mine_st = st.state + (size_t)b * st.stride;
+        const int* head = (const int*)mine_st;
+        started = __builtin_amdgcn_readfirstlane(head[0]) != 0;
+        t0 = started ? __builtin_amdgcn_readfirstlane(min(max(head[2], 0), st.cap)) : 0;
+        n = st.read ? 0 : min(n, st.cap - t0);          // no node number beyond the workspace, whatever the caller counted
+    }
+    const int cap = STREAM ? st.cap : T;                // the frames that the trie holds
+    const int OT = STREAM ? st.width : T;               // the width of an ids row
     const float* x = logits + (size_t)b * T * V;
     unsigned long long* table = (unsigned long long*)(ws + (size_t)b * region);          // [P] {key << 32 | node}, 0 = free
     unsigned* nodes = (unsigned*)(table + P);                                            // [1 + W T] parent << 7 | label
-    const int maxnode = W * T;                                                           // the largest node number
+    const int maxnode = W * cap;                                                         // the largest node number
     int Pb = BM_MINSLOTS;                               // this row's table: 2 W n slots, of the P = 2 W T that the region holds
-    while (Pb < 2 * W * n) Pb <<= 1;
+    if constexpr (STREAM) Pb = P;                       // K32: all of them, in every launch: the size enters the hash
+    else while (Pb < 2 * W * n) Pb <<= 1;
     const int shift = 32 - __builtin_ctz(Pb);
 
-    {
+    if constexpr (!STREAM) {
         uint4* tz = (uint4*)table;
         for (int i = tid; i < Pb / 2; i += BM_THREADS) tz[i] = make_uint4(0u, 0u, 0u, 0u);
     }
-    if (tid == 0) {
+    if constexpr (STREAM) {
+        if (started && wave == 0) {                     // the beam as the last launch left it, in its order
+            const int nb0 = min(max(((const int*)mine_st)[1], 0), W);
+            if (lane < nb0) {
+                const float* f = (const float*)(mine_st + BM_STATE_HEAD);
+                const int* q = (const int*)f;
+                s_pb[0][lane] = f[lane]; s_pnb[0][lane] = f[W + lane]; s_tot[0][lane] = f[2 * W + lane];
+                s_node[0][lane] = min(max(q[3 * W + lane], 0), maxnode);
+                s_par[0][lane] = min(max(q[4 * W + lane], -1), maxnode);
+                s_last[0][lane] = min(max(q[5 * W + lane], -1), V - 1);
+                s_len[0][lane] = q[6 * W + lane];       // clamped where it is reported
+                if constexpr (LM) {
+                    s_state[0][lane] = min(max(q[7 * W + lane], 0), lm.S - 1);
+                    s_lm[0][lane] = f[8 * W + lane]; s_bias[0][lane] = f[9 * W + lane];
+                }
+            }
+            if (lane == 0) s_nbeam = nb0;
+        }
+    }
+    if (tid == 0 && !started) {
         nodes[0] = 0u;
         s_pb[0][0] = 0.0f; s_pnb[0][0] = -INFINITY; s_tot[0][0] = 0.0f;
         s_node[0][0] = 0; s_par[0][0] = -1; s_last[0][0] = -1; s_len[0][0] = 0;
@@ -181,6 +237,9 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
 
     double offset = 0.0;                                // wave 0: what the rescaling has taken out of the scores so far
     double lmoff = 0.0;                                 // K25, wave 0: what it has taken out of the LM log probabilities
+    if constexpr (STREAM) {
+        if (started) { offset = ((const double*)mine_st)[2]; lmoff = ((const double*)mine_st)[3]; }
+    }
     int cur = 0;
     for (int t = 0; t < n; ++t) {
         const int nb = __builtin_amdgcn_readfirstlane(s_nbeam);
@@ -358,7 +417,7 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
                 } else {
                     pnb = tot;
                     last = c; len = s_len[cur][k] + 1; par = s_node[cur][k];
-                    const unsigned fresh = 1u + (unsigned)t * (unsigned)W + (unsigned)lane;      // <= W T
+                    const unsigned fresh = 1u + (unsigned)(t0 + t) * (unsigned)W + (unsigned)lane;       // <= W T (K32: W cap)
                     const unsigned key = (unsigned)par * 128u + (unsigned)c + 1u;                // < 2^27
                     const unsigned long long mine = ((unsigned long long)key << 32) | fresh;
                     unsigned slot = (key * 0x9E3779B1u) >> shift;
@@ -396,6 +455,30 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
         BM_BARRIER();
     }
 
+    if constexpr (STREAM) {
+        if (!st.read) {                                 // K32: store the beam; a row without frames keeps what it had, bit for bit
+            if (wave == 0 && n > 0) {
+                const int nbs = s_nbeam;
+                float* f = (float*)(mine_st + BM_STATE_HEAD);
+                int* q = (int*)f;
+                if (lane < nbs) {
+                    f[lane] = s_pb[cur][lane]; f[W + lane] = s_pnb[cur][lane]; f[2 * W + lane] = s_tot[cur][lane];
+                    q[3 * W + lane] = s_node[cur][lane]; q[4 * W + lane] = s_par[cur][lane];
+                    q[5 * W + lane] = s_last[cur][lane]; q[6 * W + lane] = s_len[cur][lane];
+                    if constexpr (LM) {
+                        q[7 * W + lane] = s_state[cur][lane]; f[8 * W + lane] = s_lm[cur][lane]; f[9 * W + lane] = s_bias[cur][lane];
+                    }
+                }
+                if (lane == 0) {
+                    int* head = (int*)mine_st;
+                    head[0] = 1; head[1] = nbs; head[2] = t0 + n; head[3] = 0;
+                    ((double*)mine_st)[2] = offset; ((double*)mine_st)[3] = lmoff;
+                }
+            }
+            return;
+        }
+    }
+
     // rank the beam by total (ties: beam order), report the first nbest
     const int nb = s_nbeam;
     if (wave == 0) {
@@ -424,7 +507,7 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
         double lmsum = 0.0, ctc64 = 0.0;
         if (lane < nb) {
             const int j = min(max(s_sel[lane], 0), BM_WMAX - 1);
-            len = min(max(s_len[cur][j], 0), n);
+            len = min(max(s_len[cur][j], 0), STREAM ? min(t0, OT) : n);       // K32: the frames so far, not this launch's
             node = s_node[cur][j];
             ctc64 = (double)s_tot[cur][j] + offset;
             sc = (float)ctc64;
@@ -441,14 +524,14 @@ __global__ __launch_bounds__(BM_THREADS) void ctc_beam_kernel(const float* __res
         s_onode[lane] = node;
     }
     __syncthreads();
-    long long* out = ids + (size_t)b * nbest * T;
+    long long* out = ids + (size_t)b * nbest * OT;
     for (int r = 0; r < nbest; ++r)
-        for (int i = s_olen[r] + tid; i < T; i += BM_THREADS) out[(size_t)r * T + i] = 0;
-    if (tid < nbest) {                                  // the labels, last to first, through the parent pointers
-        int p = s_onode[tid];
+        for (int i = s_olen[r] + tid; i < OT; i += BM_THREADS) out[(size_t)r * OT + i] = 0;
+    if (tid < nbest) {                                  // the labels, last to first, through the parent pointers: one dependent
+        int p = s_onode[tid];                           // load per label
         for (int i = s_olen[tid] - 1; i >= 0; --i) {
             const unsigned v = nodes[min(max(p, 0), maxnode)];
-            out[(size_t)tid * T + i] = (long long)(v & 127u);
+            out[(size_t)tid * OT + i] = (long long)(v & 127u);
             p = (int)(v >> 7);
         }
     }
@@ -474,8 +557,8 @@ extern "C" int v100_ctc_beam_search(const float* logits, const int* lens, void* 
     if (!logits || !ws || !ids || !ids_len || !scores) return V100_ERR_NULL;
     if (!bm_shape_ok(B, T, V, W) || nbest < 1 || nbest > W || blank < 0 || blank >= V) return V100_ERR_SHAPE;
     const unsigned vmagic = (unsigned)((1ull << 32) / (unsigned)V) + 1u;     // idx / V == umulhi(idx, vmagic) for idx < 2^13, V <= 128
-    V100_GGL(ctc_beam_kernel<false>, dim3(B), dim3(BM_THREADS), 0, (hipStream_t)stream, logits, lens, (unsigned char*)ws, ids, ids_len,
-             scores, T, V, W, nbest, blank, bm_region(T, W), bm_slots(T, W), vmagic, BmLm{});
+    V100_GGL((ctc_beam_kernel<false, false>), dim3(B), dim3(BM_THREADS), 0, (hipStream_t)stream, logits, lens, (unsigned char*)ws, ids,
+             ids_len, scores, T, V, W, nbest, blank, bm_region(T, W), bm_slots(T, W), vmagic, BmLm{}, BmStream{});
     return v100_launch_status();
 }
 
@@ -492,7 +575,76 @@ extern "C" int v100_ctc_beam_search_lm(const float* logits, const int* lens, voi
         return V100_ERR_SHAPE;
     const unsigned vmagic = (unsigned)((1ull << 32) / (unsigned)V) + 1u;
     const BmLm lm{lm_logp, lm_next, lm_final, ctc_scores, lm_scores, S, start_state, use_eos != 0, alpha, beta};
-    V100_GGL(ctc_beam_kernel<true>, dim3(B), dim3(BM_THREADS), 0, (hipStream_t)stream, logits, lens, (unsigned char*)ws, ids, ids_len,
-             scores, T, V, W, nbest, blank, bm_region(T, W), bm_slots(T, W), vmagic, lm);
+    V100_GGL((ctc_beam_kernel<true, false>), dim3(B), dim3(BM_THREADS), 0, (hipStream_t)stream, logits, lens, (unsigned char*)ws, ids,
+             ids_len, scores, T, V, W, nbest, blank, bm_region(T, W), bm_slots(T, W), vmagic, lm, BmStream{});
     return v100_launch_status();
+}
+
+// K32: the resumable form.  The caller owns two buffers, both zeroed once when the stream is created: the workspace (per row the child
+// table and the nodes, sized for max_frames frames) and the state (per row the beam between two launches).
+static inline bool bm_stream_ok(int B, int F, int V, int W) {
+    return B >= 1 && F >= 1 && V >= 2 && V <= BM_VMAX && W >= 1 && W <= BM_WMAX && (long long)W * F < (1ll << 25);
+}
+static inline long long bm_state_bytes(int W) { return (BM_STATE_HEAD + 4ll * BM_STATE_FIELDS * W + 15) & ~15ll; }
+
+extern "C" long long v100_ctc_beam_stream_workspace_bytes(int B, int max_frames, int V, int W) {
+    if (!bm_stream_ok(B, max_frames, V, W)) return -1;
+    return (long long)B * bm_region(max_frames, W);
+}
+
+extern "C" long long v100_ctc_beam_stream_state_bytes(int B, int W) {
+    if (B < 1 || W < 1 || W > BM_WMAX) return -1;
+    return (long long)B * bm_state_bytes(W);
+}
+
+template <bool LM>
+static int bm_stream_launch(const float* logits, const int* lens, void* ws, void* state, long long* ids, int* ids_len, float* scores,
+                            const BmLm& lm, int B, int T, int F, int V, int W, int nbest, int blank, int width, int read, void* stream) {
+    const unsigned vmagic = (unsigned)((1ull << 32) / (unsigned)V) + 1u;
+    const BmStream st{(unsigned char*)state, bm_state_bytes(W), F, width, read};
+    V100_GGL((ctc_beam_kernel<LM, true>), dim3(B), dim3(BM_THREADS), 0, (hipStream_t)stream, logits, lens, (unsigned char*)ws, ids,
+             ids_len, scores, T, V, W, nbest, blank, bm_region(F, W), bm_slots(F, W), vmagic, lm, st);
+    return v100_launch_status();
+}
+static inline bool bm_lm_ok(int S, int V, int start_state, float alpha, float beta) {
+    return S >= 1 && (long long)S * V <= (1ll << 28) && start_state >= 0 && start_state < S && alpha == alpha && beta == beta &&
+           fabsf(alpha) != INFINITY && fabsf(beta) != INFINITY;
+}
+
+extern "C" int v100_ctc_beam_stream_push(const float* logits, const int* lens, void* ws, void* state, int B, int T, int max_frames, int V,
+                                         int W, int blank, void* stream) {
+    if (!logits || !ws || !state) return V100_ERR_NULL;
+    if (!bm_stream_ok(B, max_frames, V, W) || T < 1 || T > BM_TMAX || blank < 0 || blank >= V) return V100_ERR_SHAPE;
+    return bm_stream_launch<false>(logits, lens, ws, state, nullptr, nullptr, nullptr, BmLm{}, B, T, max_frames, V, W, 1, blank, 1, 0,
+                                   stream);
+}
+
+extern "C" int v100_ctc_beam_stream_push_lm(const float* logits, const int* lens, void* ws, void* state, const float* lm_logp,
+                                            const int* lm_next, const float* lm_final, int S, int start_state, float alpha, float beta,
+                                            int B, int T, int max_frames, int V, int W, int blank, void* stream) {
+    if (!logits || !ws || !state || !lm_logp || !lm_next || !lm_final) return V100_ERR_NULL;
+    if (!bm_stream_ok(B, max_frames, V, W) || T < 1 || T > BM_TMAX || blank < 0 || blank >= V) return V100_ERR_SHAPE;
+    if (!bm_lm_ok(S, V, start_state, alpha, beta)) return V100_ERR_SHAPE;
+    const BmLm lm{lm_logp, lm_next, lm_final, nullptr, nullptr, S, start_state, 0, alpha, beta};
+    return bm_stream_launch<true>(logits, lens, ws, state, nullptr, nullptr, nullptr, lm, B, T, max_frames, V, W, 1, blank, 1, 0, stream);
+}
+
+extern "C" int v100_ctc_beam_stream_read(const void* ws, const void* state, long long* ids, int* ids_len, float* scores, int B,
+                                         int max_frames, int V, int W, int nbest, int width, void* stream) {
+    if (!ws || !state || !ids || !ids_len || !scores) return V100_ERR_NULL;
+    if (!bm_stream_ok(B, max_frames, V, W) || nbest < 1 || nbest > W || width < 1) return V100_ERR_SHAPE;
+    return bm_stream_launch<false>(nullptr, nullptr, (void*)ws, (void*)state, ids, ids_len, scores, BmLm{}, B, 1, max_frames, V, W, nbest, 0,
+                                   width, 1, stream);
+}
+
+extern "C" int v100_ctc_beam_stream_read_lm(const void* ws, const void* state, long long* ids, int* ids_len, float* scores,
+                                            const float* lm_final, int S, int start_state, float alpha, float beta, int final,
+                                            float* ctc_scores, float* lm_scores, int B, int max_frames, int V, int W, int nbest, int width,
+                                            void* stream) {
+    if (!ws || !state || !ids || !ids_len || !scores || !lm_final || !ctc_scores || !lm_scores) return V100_ERR_NULL;
+    if (!bm_stream_ok(B, max_frames, V, W) || nbest < 1 || nbest > W || width < 1) return V100_ERR_SHAPE;
+    if (!bm_lm_ok(S, V, start_state, alpha, beta)) return V100_ERR_SHAPE;
+    const BmLm lm{nullptr, nullptr, lm_final, ctc_scores, lm_scores, S, start_state, final != 0, alpha, beta};
+    return bm_stream_launch<true>(nullptr, nullptr, (void*)ws, (void*)state, ids, ids_len, scores, lm, B, 1, max_frames, V, W, nbest, 0,
+                                  width, 1, stream);
 }

@@ -8,7 +8,9 @@ the CTC prefix beam search, n best transcripts with their total log probabilitie
 fused form (K25): the same search with an lm.NGramLM voting inside every frame's selection, nor ctc_segment (K26): the CTC
 forward-backward over the alignments of a given transcript, reduced to time boundaries, durations and confidences per label and word,
 nor ctc_align_long (K29): the banded Viterbi that aligns a chapter-length recording to its text, nor ctc_cut_points (K31): where to
-cut a recording of any length, at its pauses, into pieces that the beam search and ctc_segment take."""
+cut a recording of any length, at its pauses, into pieces that the beam search and ctc_segment take, nor CTCBeamStream and
+ctc_beam_search_long (K32): the beam search kept between calls, so that logits can be pushed chunk by chunk and a recording of any
+length is decoded as one utterance, bit for bit what one call over all its frames would give."""
 import math
 from typing import NamedTuple, Optional
 
@@ -286,6 +288,28 @@ def edit_distance_both(hyp: torch.Tensor, hyp_len: torch.Tensor, ref: torch.Tens
     return out
 
 
+def _beam_lm_tables(who, lm, device, V, blank, lm_weight, length_bonus):
+    """The checks that ctc_beam_search and CTCBeamStream make on a language model and its weights; (logp, next, final, S, alpha, beta)
+    as the kernel takes them."""
+    tables = (getattr(lm, "logp", None), getattr(lm, "next", None), getattr(lm, "final", None))
+    if any(t is None for t in tables):
+        raise RuntimeError(f"{who}: the language model is not compiled (NGramLM.compile().to(device) first)")
+    logp, nxt, fin = tables
+    if logp.dim() != 2 or logp.shape[0] < 1 or nxt.shape != logp.shape or fin.shape != logp.shape[:1]:
+        raise RuntimeError(f"{who}: the language model is empty or malformed (logp {list(logp.shape)}, next "
+                           f"{list(nxt.shape)}, final {list(fin.shape)}; [S, V], [S, V], [S] with S >= 1 expected)")
+    if any(t.device != device for t in tables):
+        raise RuntimeError(f"{who}: the language model is on {logp.device}, the logits on {device} (lm.to(device))")
+    S = logp.shape[0]
+    if logp.shape[1] != V or S * V > 1 << 28 or not 0 <= int(lm.start) < S or blank != int(lm.blank):
+        raise RuntimeError(f"{who}: the language model has V = {logp.shape[1]}, blank = {lm.blank}, S = {S} and start state "
+                           f"{lm.start}; V = {V}, blank = {blank}, S V <= 2^28 and 0 <= start < S are required")
+    alpha, beta = float(lm_weight), float(length_bonus)
+    if not (math.isfinite(alpha) and math.isfinite(beta)):
+        raise RuntimeError(f"{who}: lm_weight = {alpha} and length_bonus = {beta} must be finite")
+    return logp.contiguous().float(), nxt.contiguous().to(torch.int32), fin.contiguous().float(), S, alpha, beta
+
+
 def ctc_beam_search(logits: torch.Tensor, lengths: torch.Tensor = None, beam_size: int = 16, nbest: int = 1, blank: int = 0, lm=None,
                     lm_weight: float = 0.5, length_bonus: float = 0.0, use_eos: bool = True):
     """CTC prefix beam search in one launch (K24, csrc/beam.hip): logits [B, T, V] fp32 (the model's output, as ctc_greedy_decode takes
@@ -315,23 +339,7 @@ def ctc_beam_search(logits: torch.Tensor, lengths: torch.Tensor = None, beam_siz
     if lens is not None and lens.numel() != B:
         raise RuntimeError(f"ctc_beam_search: lengths must have {B} elements")
     if lm is not None:
-        tables = (getattr(lm, "logp", None), getattr(lm, "next", None), getattr(lm, "final", None))
-        if any(t is None for t in tables):
-            raise RuntimeError("ctc_beam_search: the language model is not compiled (NGramLM.compile().to(device) first)")
-        logp, nxt, fin = tables
-        if logp.dim() != 2 or logp.shape[0] < 1 or nxt.shape != logp.shape or fin.shape != logp.shape[:1]:
-            raise RuntimeError(f"ctc_beam_search: the language model is empty or malformed (logp {list(logp.shape)}, next "
-                               f"{list(nxt.shape)}, final {list(fin.shape)}; [S, V], [S, V], [S] with S >= 1 expected)")
-        if any(t.device != logits.device for t in tables):
-            raise RuntimeError(f"ctc_beam_search: the language model is on {logp.device}, the logits on {logits.device} (lm.to(device))")
-        S = logp.shape[0]
-        if logp.shape[1] != V or S * V > 1 << 28 or not 0 <= int(lm.start) < S or blank != int(lm.blank):
-            raise RuntimeError(f"ctc_beam_search: the language model has V = {logp.shape[1]}, blank = {lm.blank}, S = {S} and start state "
-                               f"{lm.start}; V = {V}, blank = {blank}, S V <= 2^28 and 0 <= start < S are required")
-        alpha, beta = float(lm_weight), float(length_bonus)
-        if not (math.isfinite(alpha) and math.isfinite(beta)):
-            raise RuntimeError(f"ctc_beam_search: lm_weight = {alpha} and length_bonus = {beta} must be finite")
-        logp, nxt, fin = logp.contiguous().float(), nxt.contiguous().to(torch.int32), fin.contiguous().float()
+        logp, nxt, fin, S, alpha, beta = _beam_lm_tables("ctc_beam_search", lm, logits.device, V, blank, lm_weight, length_bonus)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=logits.device)
     ids = torch.empty((B, nbest, T), dtype=torch.int64, device=logits.device)
     ids_len = torch.empty((B, nbest), dtype=torch.int32, device=logits.device)
@@ -343,6 +351,141 @@ def ctc_beam_search(logits: torch.Tensor, lengths: torch.Tensor = None, beam_siz
     N.call("v100_ctc_beam_search_lm", logits, lens, ws, ids, ids_len, scores, logp, nxt, fin, S, int(lm.start), alpha, beta,
            int(bool(use_eos)), ctc_scores, lm_scores, B, T, V, W, nbest, blank)
     return ids, ids_len, scores, ctc_scores, lm_scores
+
+
+class CTCBeamStream:
+    """ctc_beam_search without a frame limit (K32, the resumable form of csrc/beam.hip): the beam survives between calls, so logits
+    can be pushed as they arrive, and any split of a recording into pushes gives ctc_beam_search's result on all the frames bit for
+    bit -- the beam is not restarted, the language model keeps one context, no word is split.
+
+        s = CTCBeamStream(batch, vocab, beam_size, lm=lm, max_frames=90000)
+        s.push(logits [B, T, V], lengths)      any 1 <= T <= 4096 per call; row b runs clamp(lengths[b], 0, T) more frames
+        s.hypotheses(nbest)                    the n best so far, ctc_beam_search's tuple (five tensors with an LM)
+        s.finish(nbest)                        the same with the LM's end-of-sentence term (use_eos), and the stream is closed
+
+    hypotheses() runs no frame and stores nothing: it may be called at any time, and twice.  Its ids are [B, nbest, frames pushed],
+    zero padded; without final=True the end-of-sentence term is left out, whatever use_eos says.  Reading the labels back is one
+    dependent load per label of each hypothesis, so reading after every short push of a long recording costs more than the pushes.
+    A row whose length is 0 in a push keeps its state untouched.
+
+    Memory: the prefix trie must persist (the beam's common prefix does not grow: old hypotheses with one early deletion are never
+    displaced), and its table's size enters the hash, so the capacity max_frames is fixed here: per row 4 (1 + W max_frames) bytes of
+    nodes and 8 bytes per slot of the power of two >= 2 W max_frames, 20 to 36 bytes x beam_size x max_frames -- 30 to 50 MB for
+    a 30-minute recording (90000 frames) at beam 16.  Every push counts its T frames against max_frames, whatever the lengths say,
+    and a push beyond it raises before anything is launched.  beam_size x max_frames < 2^25 (524k frames at beam 64, 2M at 16).
+    The other limits, and the checks on the arguments, are ctc_beam_search's."""
+
+    def __init__(self, batch: int, vocab: int, beam_size: int = 16, blank: int = 0, lm=None, lm_weight: float = 0.5,
+                 length_bonus: float = 0.0, use_eos: bool = True, max_frames: int = 65536, device=None):
+        if device is None:
+            device = lm.logp.device if getattr(lm, "logp", None) is not None else "cuda"
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("CTCBeamStream: GPU tensors only")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        B, V, W, F, blank = int(batch), int(vocab), int(beam_size), int(max_frames), int(blank)
+        nbytes = N.helper("v100_ctc_beam_stream_workspace_bytes", B, F, V, W)
+        if nbytes <= 0 or not 0 <= blank < V:
+            raise RuntimeError(f"CTCBeamStream: unsupported shape or argument (batch = {B} >= 1, 2 <= vocab = {V} <= 128, 1 <= beam_size "
+                               f"= {W} <= 64, max_frames = {F} >= 1 with beam_size * max_frames < 2^25 and 0 <= blank = {blank} < "
+                               "vocab are the limits)")
+        self.lm = None
+        if lm is not None:
+            self.lm = _beam_lm_tables("CTCBeamStream", lm, device, V, blank, lm_weight, length_bonus) + (int(lm.start),)
+        self.batch, self.vocab, self.beam_size, self.blank, self.max_frames, self.device = B, V, W, blank, F, device
+        self.use_eos, self.frames, self.closed = bool(use_eos), 0, False
+        self._ws = torch.zeros((nbytes,), dtype=torch.uint8, device=device)
+        self._state = torch.zeros((N.helper("v100_ctc_beam_stream_state_bytes", B, W),), dtype=torch.uint8, device=device)
+
+    def push(self, logits: torch.Tensor, lengths: torch.Tensor = None) -> None:
+        if self.closed:
+            raise RuntimeError("CTCBeamStream.push: the stream is finished")
+        if not logits.is_cuda or (lengths is not None and not lengths.is_cuda):
+            raise RuntimeError("CTCBeamStream.push: GPU tensors only")
+        B, V = self.batch, self.vocab
+        if logits.dim() != 3 or logits.shape[0] != B or logits.shape[2] != V or not 1 <= logits.shape[1] <= 4096:
+            raise RuntimeError(f"CTCBeamStream.push: logits must be [{B}, T, {V}] with 1 <= T <= 4096, got {list(logits.shape)}")
+        if logits.device != self.device:
+            raise RuntimeError(f"CTCBeamStream.push: the logits are on {logits.device}, the stream on {self.device}")
+        T = logits.shape[1]
+        if self.frames + T > self.max_frames:
+            raise RuntimeError(f"CTCBeamStream.push: {self.frames} frames pushed and {T} more exceed max_frames = {self.max_frames}")
+        logits = logits.contiguous().float()
+        lens = lengths.to(device=self.device, dtype=torch.int32).contiguous() if lengths is not None else None
+        if lens is not None and lens.numel() != B:
+            raise RuntimeError(f"CTCBeamStream.push: lengths must have {B} elements")
+        if self.lm is None:
+            N.call("v100_ctc_beam_stream_push", logits, lens, self._ws, self._state, B, T, self.max_frames, V, self.beam_size, self.blank)
+        else:
+            logp, nxt, fin, S, alpha, beta, start = self.lm
+            N.call("v100_ctc_beam_stream_push_lm", logits, lens, self._ws, self._state, logp, nxt, fin, S, start, alpha, beta, B, T,
+                   self.max_frames, V, self.beam_size, self.blank)
+        self.frames += T
+
+    def hypotheses(self, nbest: int = 1, final: bool = False):
+        if self._ws is None:
+            raise RuntimeError("CTCBeamStream.hypotheses: the stream is finished")
+        B, W, nbest = self.batch, self.beam_size, int(nbest)
+        if not 1 <= nbest <= W:
+            raise RuntimeError(f"CTCBeamStream.hypotheses: 1 <= nbest = {nbest} <= beam_size = {W} is required")
+        width = max(self.frames, 1)                      # before the first push the ids are [B, nbest, 0]: a view of one column
+        ids = torch.empty((B, nbest, width), dtype=torch.int64, device=self.device)
+        ids_len = torch.empty((B, nbest), dtype=torch.int32, device=self.device)
+        scores = torch.empty((B, nbest), dtype=torch.float32, device=self.device)
+        if self.lm is None:
+            N.call("v100_ctc_beam_stream_read", self._ws, self._state, ids, ids_len, scores, B, self.max_frames, self.vocab, W, nbest, width)
+            return ids[:, :, :self.frames], ids_len, scores
+        _, _, fin, S, alpha, beta, start = self.lm
+        ctc_scores, lm_scores = torch.empty_like(scores), torch.empty_like(scores)
+        N.call("v100_ctc_beam_stream_read_lm", self._ws, self._state, ids, ids_len, scores, fin, S, start, alpha, beta,
+               int(bool(final) and self.use_eos), ctc_scores, lm_scores, B, self.max_frames, self.vocab, W, nbest, width)
+        return ids[:, :, :self.frames], ids_len, scores, ctc_scores, lm_scores
+
+    def finish(self, nbest: int = 1):
+        """hypotheses(nbest, final=True); the stream is closed and its buffers are released."""
+        out = self.hypotheses(nbest, final=True)
+        self.closed, self._ws, self._state = True, None, None
+        return out
+
+
+def beam_chunk_plan(T: int, chunk: int):
+    """How ctc_beam_search_long cuts T frames: [(start, frames)], `chunk` frames each but the last, every frame exactly once."""
+    if T < 1 or not 1 <= chunk <= 4096:
+        raise ValueError("beam_chunk_plan: T >= 1 and 1 <= chunk <= 4096 are required")
+    return [(start, min(chunk, T - start)) for start in range(0, T, chunk)]
+
+
+def beam_chunk_lengths(lengths: torch.Tensor, start: int, frames: int) -> torch.Tensor:
+    """The rows' lengths inside the chunk [start, start + frames): clamp(length - start, 0, frames)."""
+    return (lengths - start).clamp(0, frames)
+
+
+def ctc_beam_search_long(logits: torch.Tensor, lengths: torch.Tensor = None, beam_size: int = 16, nbest: int = 1, blank: int = 0,
+                         lm=None, lm_weight: float = 0.5, length_bonus: float = 0.0, use_eos: bool = True, chunk: int = 4096):
+    """ctc_beam_search on any number of frames: a CTCBeamStream sized for T, one push per `chunk` frames (beam_chunk_plan; row b has
+    clamp(length_b - start, 0, frames) frames in a chunk), then finish(nbest).  Arguments, return values and their shapes are
+    ctc_beam_search's, and so are the bits, whatever `chunk` is: at T <= 4096 the two calls agree exactly.  One workgroup per row
+    walks its frames one after the other (K24's 3 to 11 us a frame), so a long recording is decoded serially: much slower than
+    LongASRPipeline.segments' batch of pieces, and exact, with one language-model context.
+    Limits: ctc_beam_search's on B, V, beam_size, nbest and blank; T >= 1 with beam_size * T < 2^25; 1 <= chunk <= 4096.
+    Memory: see CTCBeamStream (20 to 36 bytes x beam_size x T per row)."""
+    if not logits.is_cuda or (lengths is not None and not lengths.is_cuda):
+        raise RuntimeError("ctc_beam_search_long: GPU tensors only")
+    if logits.dim() != 3:
+        raise RuntimeError(f"ctc_beam_search_long: logits must be [B, T, V], got {list(logits.shape)}")
+    B, T, V = logits.shape
+    W, nbest, blank, chunk = int(beam_size), int(nbest), int(blank), int(chunk)
+    if B < 1 or T < 1 or not 1 <= nbest <= W or not 1 <= chunk <= 4096:
+        raise RuntimeError(f"ctc_beam_search_long: unsupported shape or argument (B = {B} >= 1, T = {T} >= 1, 1 <= nbest = {nbest} <= "
+                           f"beam_size = {W} and 1 <= chunk = {chunk} <= 4096 are the limits)")
+    lens = lengths.to(device=logits.device, dtype=torch.int32).contiguous() if lengths is not None else None
+    if lens is not None and lens.numel() != B:
+        raise RuntimeError(f"ctc_beam_search_long: lengths must have {B} elements")
+    stream = CTCBeamStream(B, V, W, blank, lm, lm_weight, length_bonus, use_eos, max_frames=T, device=logits.device)
+    for start, frames in beam_chunk_plan(T, chunk):
+        stream.push(logits[:, start:start + frames], None if lens is None else beam_chunk_lengths(lens.reshape(-1), start, frames))
+    return stream.finish(nbest)
 
 
 class CTCSegments(NamedTuple):

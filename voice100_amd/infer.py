@@ -749,12 +749,14 @@ class LongASRPipeline:
     pieces.  Cutting inside a run of blank frames costs the greedy decode nothing (CTC never merges labels across a blank: the
     pieces' decodes, concatenated, are the recording's); the beam search loses only what it would have carried across the pause,
     and THE LANGUAGE MODEL'S CONTEXT RESTARTS AT EVERY CUT: each segment is scored as a sentence of its own.  A forced cut (a
-    stretch of max_frames frames without an admissible pause) may split a word; its segment says so in "forced".
+    stretch of max_frames frames without an admissible pause) may split a word; its segment says so in "forced".  whole() (K32) has
+    none of the three: it decodes the recording as one utterance with a resumable beam, one frame after the other, at many times
+    the cost and without confidences.
     An ASRPipeline is held and called for the decode; blank must be 0, as there.  Eval mode only, like windowed_logits.
     Device-to-host copies: the number of segments S, one copy of the calls' widths, and the longest hypothesis of each call."""
 
     def __init__(self, model, mel=None, beam_size=None, lm=None, lm_weight=0.5, length_bonus=0.0, keep=1500, max_frames=3000, min_gap=25,
-                 margin=0.0, pad=5, min_frames=50, max_batch=32, blank=0, sep=1, frame_seconds=None):
+                 margin=0.0, pad=5, min_frames=50, max_batch=32, blank=0, sep=1, frame_seconds=None, band=2048):
         if int(blank) != 0:
             raise RuntimeError(f"LongASRPipeline: blank = {blank}; the decode of ASRPipeline takes the blank at id 0")
         if int(max_batch) < 1:
@@ -763,6 +765,7 @@ class LongASRPipeline:
                                frame_seconds=frame_seconds)
         self.model, self.mel = model, mel
         self.keep, self.max_batch, self.blank, self.sep = int(keep), int(max_batch), int(blank), sep
+        self.band = int(band)                                # whole(): ctc_align_long's band
         self.cut = dict(max_frames=int(max_frames), min_gap=min_gap, margin=float(margin), pad=int(pad), min_frames=int(min_frames))
 
     def _wave(self, path_or_wave, who):
@@ -890,6 +893,67 @@ class LongASRPipeline:
                          "score": float(score[i]), "forced": bool(forced[i]), "words": words})
         whole = join_ids([ids[i, :int(n[i])].tolist() for i in range(ids.shape[0])], self.sep)
         return {"text": decode(torch.tensor(whole, dtype=torch.int64)), "utterances": utts, "frame_seconds": fs}
+
+    @torch.no_grad()
+    def whole(self, path_or_wave=None, feats: torch.Tensor = None, logits: torch.Tensor = None, timed: bool = True, chunk: int = 4096):
+        """The recording decoded as ONE utterance (K32): windowed_logits, then decode.ctc_beam_search_long over all its frames -- the
+        beam is never restarted, the language model keeps one context, no cut can split a word -- and with timed=True
+        decode.ctc_align_long of the best transcript on the log-softmax of the same logits (band = the constructor's).  The inputs
+        are segments()'.  Needs a beam_size: the greedy decode of the pieces already concatenates to the recording's.  One workgroup
+        walks the frames one after the other, so this is much slower than segments() (see decode.ctc_beam_search_long), and its
+        memory grows with the recording.  Returns a dict of device tensors: "ids" [L] int64 and "ids_len", "score" (0-dim; the fused
+        score with a language model, then also "ctc_score" and "lm_score"); with timed "start", "end" [L] int32 = each label's first
+        frame and one past its last on the best path (the cumulative sum of the aligner's frames per position) and "ok" (0-dim
+        int32; 0: the band lost the path, start = end = 0 -- widen band); and "frame_seconds".  There are NO confidences:
+        ctc_segment, which computes them, stops at 4096 frames.  One read-back, of ids_len, sizes L."""
+        from .decode import ctc_align_long, ctc_beam_search_long
+        a = self.asr
+        if a.beam_size is None:
+            raise RuntimeError("LongASRPipeline.whole: the pipeline decodes greedily, and the greedy decodes of segments()' pieces "
+                               "already concatenate to the recording's exactly (pass beam_size=)")
+        if logits is None:
+            if feats is None:
+                feats = self.mel(self._wave(path_or_wave, "whole").reshape(1, -1))[0]
+            logits = windowed_logits(self.model, feats, self.keep)
+        if not logits.is_cuda:
+            raise RuntimeError("LongASRPipeline.whole: GPU tensors only")
+        if logits.dim() != 2:
+            raise RuntimeError(f"LongASRPipeline.whole: logits must be [T', V], got {list(logits.shape)}")
+        logits = logits.contiguous().float()
+        res = ctc_beam_search_long(logits[None], None, a.beam_size, 1, self.blank, a.lm, a.lm_weight, a.length_bonus, chunk=chunk)
+        n = res[1][0, 0]
+        L = max(int(n), 1)                                   # the one read-back
+        ids = res[0][0, 0, :L].contiguous()
+        out = {"ids": ids, "ids_len": n, "score": res[2][0, 0]}
+        if a.lm is not None:
+            out.update({"ctc_score": res[3][0, 0], "lm_score": res[4][0, 0]})
+        if timed:
+            al = ctc_align_long(torch.log_softmax(logits, dim=-1)[None], ids[None], None, n.reshape(1), band=self.band, blank=self.blank)
+            ends = torch.cumsum(al.align[0], 0, dtype=torch.int32)[1:2 * L:2]        # label i sits at extended position 2 i + 1
+            out.update({"start": ends - al.align[0, 1:2 * L:2], "end": ends, "ok": al.ok[0]})
+        out["frame_seconds"] = self._frame_seconds()
+        return out
+
+    def transcribe_whole(self, path, decode: Callable[[torch.Tensor], str]):
+        """A WAV / FLAC file -> {"text", "words": [{"word", "start", "end"}], "score", "frame_seconds"} from whole(): times in seconds,
+        an end cut at the file's own duration, a word a maximal run of labels other than the separator, `decode` the caller's
+        tokenizer.decode (ids tensor -> str).  No confidences (see whole()).  Needs a `mel` and a separator id."""
+        if self.sep is None:
+            raise RuntimeError("LongASRPipeline.transcribe_whole: words need a separator id (whole() gives the label level)")
+        wave = self._wave(path, "transcribe_whole")
+        out = self.whole(wave)
+        fs = out["frame_seconds"]
+        seconds = wave.shape[0] / self.mel.sample_rate
+        n = int(out["ids_len"])
+        ids, start, end = (out[k].cpu()[:n] for k in ("ids", "start", "end"))
+        words, first = [], None
+        for i in range(n + 1):
+            if i < n and int(ids[i]) != self.sep:
+                first = i if first is None else first
+            elif first is not None:
+                words.append({"word": decode(ids[first:i]), "start": int(start[first]) * fs, "end": min(int(end[i - 1]) * fs, seconds)})
+                first = None
+        return {"text": decode(ids), "words": words, "score": float(out["score"]), "frame_seconds": fs}
 
 
 def long_transcript_records(result) -> List[str]:
