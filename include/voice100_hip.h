@@ -336,6 +336,11 @@ int v100_pw_wgrad_io(const void* G, const void* G2, const float* ga, const float
 int v100_pw_wgrad_group_supported(int B, int M, int K, int T, int S, int g_mode, int x_mode, int io16);
 int v100_pw_wgrad_group_tiles(int M, int K, int x_mode);
 int v100_pw_wgrad_group(int n, const void* const* ptrs, const int* dims, void* stream);
+/* The same launch on 128 x 128 tiles (csrc/pointwise_bf16_wgrad_small.h), for gradients with too few of the tiles above to fill the
+ * chip (256 x 1024: 8 of those, 16 of these): both x_modes with M % 128 == 0 and K % 128 == 0, same tables, same bit-identity. */
+int v100_pw_wgrad_group_small_supported(int B, int M, int K, int T, int S, int g_mode, int x_mode, int io16);
+int v100_pw_wgrad_group_small_tiles(int M, int K, int x_mode);
+int v100_pw_wgrad_group_small(int n, const void* const* ptrs, const int* dims, void* stream);
 int v100_dw_mfma_supported(int K, int stride);
 /* Row pitch, in elements, of every 16-bit-stored activation tensor [B][C][P] the _io entry points address: a multiple of 8 (16-byte
  * rows); for B > 1 and T >= 256 a multiple of 64 (rows start on 128-byte lines: a time-stretched 1136-byte row otherwise shares its
@@ -510,6 +515,14 @@ int v100_ir_stack_bwd(const int* desc, const void* const* params, const void* x,
  * changes bwd_ws_bytes of v100_ir_stack_plan, so set it before planning. */
 int v100_ir_stack_wgrad_plan(const int* desc, int have_x16, int min_problem_tiles, int min_flush_tiles, long long* out);
 int v100_ir_stack_wgrad_group_thresholds(int min_problem_tiles, int min_flush_tiles);
+/* Tier 2: once such a flush is enqueued its blocks' regions are dead, and a later block of the walk below min_problem_tiles whose
+ * gradients qualify for v100_pw_wgrad_group_small parks its da3 / da1 there (first fit; no bytes of its own) and waits for one
+ * small-tile launch: where the next block cannot join, at 16 problems, or where the walk ends -- grouped if >= min_flush_small
+ * workgroups (96) wait, else per problem.  A stack without a tier-1 flush behaves as before.  v100_ir_stack_wgrad_plan2: the same
+ * table for tier 2 ({defers, byte offset of the borrowed region or -1, flush: workgroups}), then the same two totals.
+ * v100_ir_stack_wgrad_group2_threshold sets min_flush_small process-wide; 0 turns tier 2 off. */
+int v100_ir_stack_wgrad_plan2(const int* desc, int have_x16, int min_problem_tiles, int min_flush_tiles, int min_flush_small, long long* out);
+int v100_ir_stack_wgrad_group2_threshold(int min_flush_small);
 
 /* ---- SURVEY 8(f) "next" rows: integer decode / alignment steps on the device (csrc/decode.hip), bit-exact ----
  * greedy CTC decode: argmax per frame (first maximum), collapse repeats, drop blanks (voice100/text.py:99-104);

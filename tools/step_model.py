@@ -32,6 +32,7 @@ SPEC = [  # (cin, cout, k, stride, residual)   asr.py:62-82 with hidden_size = 5
 ]
 VOCAB, N_MEL, TEXT_LEN = 29, 64, 100
 N_PARAMS = 11621661
+TIER2 = True        # the narrow blocks' weight gradients wait for a small-tile grouped launch (v100_ir_stack_wgrad_group2_threshold > 0)
 
 
 def pitch16(t):
@@ -55,7 +56,12 @@ def step_rows(B=32, T=1024):
     add("optim", "weight preparation: fp32 weights -> bf16 + transposed bf16 copies (1x1 weights only)", 0)      # filled below
     t = T
     w_pw = 0
-    n_grouped = 0
+    n_grouped = n_small = 0
+    # blocks whose two weight gradients wait for the grouped launch (the test further down, ahead of the walk)
+    wide, tw = [], T
+    for i, (cin, cout, k, s, res) in enumerate(SPEC):
+        tw = (tw - 1) // s + 1
+        wide.append(s == 1 and i > 0 and tw <= 512 and B <= 32 and (cout // 256) * (4 * cin // 128) >= 32 and (4 * cin // 128) * (cin // 256) >= 32)
     for i, (cin, cout, k, s, res) in enumerate(SPEC):
         hid = 4 * cin
         tout = (t - 1) // s + 1
@@ -91,7 +97,12 @@ def step_rows(B=32, T=1024):
         # contraction (block.hip, v100_ir_stack_bwd; pointwise_bf16_wgrad_group.h): same operand bytes, no partial slabs, no reduction
         grouped = a16 and i > 0 and tout <= 512 and B <= 32 and (cout // 256) * (hid // 128) >= 32 and (hid // 128) * (cin // 256) >= 32
         n_grouped += 2 * grouped
-        how3 = "in the grouped launch" if grouped else f"through {S3} partial slabs"
+        # tier 2: a narrower block BELOW a wide one parks da3 / da1 in a region the grouped launch has left dead and its gradients go in
+        # ONE launch on 128 x 128 tiles where the walk leaves the stride-1 blocks (pointwise_bf16_wgrad_small.h): no slabs either
+        small = TIER2 and not grouped and a16 and i > 0 and tout <= 512 and B <= 32 and any(wide[i + 1:]) and not (cin % 128 or cout % 128)
+        n_small += 2 * small
+        grouped = grouped or small
+        how3 = "in the small-tile grouped launch" if small else "in the grouped launch" if grouped else f"through {S3} partial slabs"
         add("pw_wgrad", f"{L} project weight gradient: da3, a2 -> dW3 ({how3})", B * cout * Po * e + B * hid * Po * e + cout * hid * 4, fl3,
             launches=0 if grouped else 1)
         if not grouped:
@@ -100,7 +111,7 @@ def step_rows(B=32, T=1024):
             B * cout * Po * e + cout * hid * 2 + 2 * B * hid * Po * e + parts_o * hid * 8, fl3)
         add("dw_bwd", f"{L} depthwise backward (data + weight fused): dz2, a2, a1 -> dz1, dWd",
             e * B * hid * (2 * Po + 2 * Pi) + 8 * hid * k + 8 * hid)
-        how1 = "dW1 in the grouped launch" if grouped else "dW1 partial slabs"
+        how1 = "dW1 in the small-tile grouped launch" if small else "dW1 in the grouped launch" if grouped else "dW1 partial slabs"
         add("pw_wgrad", f"{L} expand weight gradient: dz1, a1 (BN1-backward affine), x -> {how1}",
             2 * B * hid * Pi * e + xin + hid * cin * 4, fl1, launches=0 if grouped else 1)
         if not grouped:
@@ -113,6 +124,8 @@ def step_rows(B=32, T=1024):
         t = tout
     if n_grouped:
         add("pw_wgrad", f"the grouped launch of the {n_grouped} weight gradients above (their bytes and flops are in their rows)", 0)
+    if n_small:
+        add("pw_wgrad", f"the small-tile grouped launch of the {n_small} weight gradients above (their bytes and flops are in their rows)", 0)
     # ---- head, loss
     Th = t
     # round 6: dropout's backward rides in the head's backward-data GEMM (one byte of mask per element there), the CTC gradient is

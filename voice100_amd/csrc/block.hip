@@ -191,14 +191,29 @@ static size_t ir_defer_bytes(const IrShape& s) { return ir_defer_da3_bytes(s) + 
 static int ir_wgrad_defer_tiles(const IrShape& s) {      // of both gradients
     return v100_pw_wgrad_group_tiles(s.cout, s.hid, 1) + v100_pw_wgrad_group_tiles(s.hid, s.cin, 0);
 }
-static bool ir_wgrad_defer_ok(const IrShape& s, bool have_x16, int min_tiles) {
-    const int B = s.B, cin = s.cin, hid = s.hid, cout = s.cout, T = s.T, K = s.K;
+// (what decides that ir_bwd has finished da3 / da1 to park: everything but the gradients' tiles)
+static bool ir_wgrad_defer_path(const IrShape& s, bool have_x16) {
+    const int B = s.B, hid = s.hid, T = s.T, K = s.K;
     if (s.act16 < 4 || !s.shadows || s.frozen || !have_x16 || s.S != 1) return false;
-    if (!ir_act16_supported(s) || v100_dw_num_groups(B, hid) != 1 || !dw_bwd_da1_supported(B, hid, T, K, 1)) return false;
+    return ir_act16_supported(s) && v100_dw_num_groups(B, hid) == 1 && dw_bwd_da1_supported(B, hid, T, K, 1);
+}
+static bool ir_wgrad_defer_ok(const IrShape& s, bool have_x16, int min_tiles) {
+    const int B = s.B, cin = s.cin, hid = s.hid, cout = s.cout, T = s.T;
+    if (!ir_wgrad_defer_path(s, have_x16)) return false;
     const int io = WG_IO_G | WG_IO_X;
     return v100_pw_wgrad_group_supported(B, cout, hid, T, v100_pw_wgrad_splits(B, cout, hid), 0, 1, io) &&
            v100_pw_wgrad_group_supported(B, hid, cin, T, v100_pw_wgrad_splits(B, hid, cin), 0, 0, io) &&
            v100_pw_wgrad_group_tiles(cout, hid, 1) >= min_tiles && v100_pw_wgrad_group_tiles(hid, cin, 0) >= min_tiles;
+}
+// Tier 2: a block below tier 1's tile minimum whose gradients are problems of the 128 x 128 launch (v100_pw_wgrad_group_small)
+static bool ir_wgrad_defer_small_ok(const IrShape& s, bool have_x16) {
+    const int B = s.B, cin = s.cin, hid = s.hid, cout = s.cout, T = s.T, io = WG_IO_G | WG_IO_X;
+    return ir_wgrad_defer_path(s, have_x16) &&
+           v100_pw_wgrad_group_small_supported(B, cout, hid, T, v100_pw_wgrad_splits(B, cout, hid), 0, 1, io) &&
+           v100_pw_wgrad_group_small_supported(B, hid, cin, T, v100_pw_wgrad_splits(B, hid, cin), 0, 0, io);
+}
+static int ir_wgrad_defer_small_tiles(const IrShape& s) {
+    return v100_pw_wgrad_group_small_tiles(s.cout, s.hid, 1) + v100_pw_wgrad_group_small_tiles(s.hid, s.cin, 0);
 }
 
 extern "C" long long v100_ir_bwd_workspace_bytes(const int* shape) {
@@ -431,7 +446,8 @@ extern "C" int v100_ir_stack_fwd_eval(int n, const int* shapes, const void* cons
 // All activations the run keeps for backward live in ONE caller-allocated blob laid out by v100_ir_stack_plan; backward walks the
 // blocks in reverse with one shared workspace and two ping-pong gradient buffers.  Pure sequencing of ir_fwd_train / ir_bwd
 // (same kernels, same order, bit-identical results) -- except that backward runs the wide blocks' 1x1 weight gradients later, several
-// blocks' in one grouped launch (stack_flush_plan; the same sums in the same order, bit-identical too).
+// blocks' in one grouped launch (stack_flush_plan; the same sums in the same order, bit-identical too), and the narrow blocks below
+// them in a second one on smaller tiles (stack_flush_plan2).
 // desc, plan and params: include/voice100_hip.h; the plan ends with {blob_bytes, bwd_ws_bytes, grad_floats, fwd_ws_offset, 0, 0}
 enum { ST_N, ST_B, ST_T, ST_BF16, ST_LEVEL, ST_SHADOW, ST_HDR };
 namespace {
@@ -512,6 +528,54 @@ void stack_flush_plan(const StackBlock* blk, int n, bool have_x16, int min_flush
         }
     }
 }
+
+// Tier 2 (narrow blocks): once a tier-1 flush is enqueued, the flushed blocks' regions are dead, and a later block of the walk
+// whose gradients are problems of the 128 x 128 launch parks ITS da3 / da1 there (first fit, 256-aligned; same stream, so the
+// flush has read a region before the block writes it): no regions of its own, no new bytes.  off2[i]: byte offset of block i's
+// borrowed region (-1: it does not defer); flush2[i]: workgroups flushed right after block i's backward, > 0 in one small-tile
+// launch, < 0 (fewer than min_small) through the per-problem launches.  A tier-2 flush falls where the next block cannot join,
+// at WG_GROUP_MAX problems, and where the walk ends; it returns what tier 2 borrowed.  min_small 0: tier 2 off.
+int wg_min_flush_small = 96;
+void stack_flush_plan2(const StackBlock* blk, int n, bool have_x16, const bool* defer, const int* flush, int min_small, long long* off2,
+                       int* flush2) {
+    struct Span { long long off; size_t bytes; };
+    Span dead[32], avail[32];                              // regions of flushed tier-1 blocks; what is left of them
+    int ndead = 0, wait1[32], nwait1 = 0;                  // tier-1 blocks not flushed yet
+    int wgs = 0, count = 0;
+    auto end2 = [&](int at) {
+        flush2[at] = wgs >= min_small ? wgs : -wgs;
+        wgs = count = 0;
+        for (int j = 0; j < ndead; ++j) avail[j] = dead[j];
+    };
+    for (int i = n - 1; i >= 0; --i) {
+        off2[i] = -1;
+        flush2[i] = 0;
+        const size_t need = ir_defer_bytes(blk[i].s);
+        const bool can = min_small > 0 && !defer[i] && ir_wgrad_defer_small_ok(blk[i].s, i > 0 ? blk[i - 1].y16 >= 0 : have_x16);
+        auto first_fit = [&]() {
+            for (int j = 0; can && j < ndead; ++j)
+                if (avail[j].bytes >= need) return j;
+            return -1;
+        };
+        int slot = first_fit();
+        if (slot < 0 && count) {                           // (count > 0: block i + 1 joined, so i + 1 < n)
+            end2(i + 1);
+            slot = first_fit();                            // (the regions were full: a new list starts here)
+        }
+        if (slot >= 0) {
+            off2[i] = avail[slot].off;
+            avail[slot].off += (long long)need; avail[slot].bytes -= need;      // (ir_defer_bytes is a multiple of 256)
+            wgs += ir_wgrad_defer_small_tiles(blk[i].s);
+            count += 2;
+            if (i == 0 || count + 2 > 16) end2(i);
+        }
+        if (defer[i]) wait1[nwait1++] = i;
+        if (flush[i]) {
+            for (int j = 0; j < nwait1; ++j) dead[ndead] = avail[ndead] = Span{blk[wait1[j]].defer_off, ir_defer_bytes(blk[wait1[j]].s)}, ++ndead;
+            nwait1 = 0;
+        }
+    }
+}
 }   // namespace
 
 // Test hook: the least tiles of a gradient that defers (32) and of a grouped flush (192).  The defaults are what fills the chip;
@@ -520,6 +584,13 @@ extern "C" int v100_ir_stack_wgrad_group_thresholds(int min_problem_tiles, int m
     if (min_problem_tiles < 1 || min_flush_tiles < 1) return V100_ERR_SHAPE;
     wg_min_problem_tiles = min_problem_tiles;
     wg_min_flush_tiles = min_flush_tiles;
+    return V100_OK;
+}
+
+// The least workgroups of a tier-2 (small-tile) flush that go in one launch (stack_flush_plan2); 0 turns tier 2 off.
+extern "C" int v100_ir_stack_wgrad_group2_threshold(int min_flush_small) {
+    if (min_flush_small < 0) return V100_ERR_SHAPE;
+    wg_min_flush_small = min_flush_small;
     return V100_OK;
 }
 
@@ -538,6 +609,28 @@ extern "C" int v100_ir_stack_wgrad_plan(const int* desc, int have_x16, int min_p
     size_t shared = t.bwd_ws;
     for (int i = 0; i < n; ++i) {
         out[3 * i] = defer[i]; out[3 * i + 1] = blk[i].defer_off; out[3 * i + 2] = flush[i];
+        if (blk[i].defer_off >= 0 && (size_t)blk[i].defer_off < shared) shared = (size_t)blk[i].defer_off;
+    }
+    out[3 * n] = (long long)t.bwd_ws; out[3 * n + 1] = (long long)shared;
+    return V100_OK;
+}
+
+// As v100_ir_stack_wgrad_plan, for tier 2: out = 3 per block {defers to the small-tile launch, byte offset of the region it borrows
+// (-1: none), flush (stack_flush_plan2)}; then the same two totals (tier 2 adds no bytes).
+extern "C" int v100_ir_stack_wgrad_plan2(const int* desc, int have_x16, int min_problem_tiles, int min_flush_tiles, int min_flush_small,
+                                         long long* out) {
+    if (!desc || !out) return V100_ERR_NULL;
+    if (min_problem_tiles < 1 || min_flush_tiles < 1 || min_flush_small < 0) return V100_ERR_SHAPE;
+    StackBlock blk[32];
+    StackTotals t;
+    if (!stack_layout(desc, blk, t, min_problem_tiles)) return V100_ERR_SHAPE;
+    const int n = desc[ST_N];
+    bool defer[32]; int flush[32], flush2[32]; long long off2[32];
+    stack_flush_plan(blk, n, have_x16 != 0, min_flush_tiles, defer, flush);
+    stack_flush_plan2(blk, n, have_x16 != 0, defer, flush, min_flush_small, off2, flush2);
+    size_t shared = t.bwd_ws;
+    for (int i = 0; i < n; ++i) {
+        out[3 * i] = off2[i] >= 0; out[3 * i + 1] = off2[i]; out[3 * i + 2] = flush2[i];
         if (blk[i].defer_off >= 0 && (size_t)blk[i].defer_off < shared) shared = (size_t)blk[i].defer_off;
     }
     out[3 * n] = (long long)t.bwd_ws; out[3 * n + 1] = (long long)shared;
@@ -625,10 +718,17 @@ extern "C" int v100_ir_stack_bwd(const int* desc, const void* const* params, con
     // CU through the whole contraction, instead of a split-K launch + slab reduction each.  Same sums in the same order.
     bool defer[32]; int flush[32];
     stack_flush_plan(blk, n, x16 != nullptr, wg_min_flush_tiles, defer, flush);
-    const void* gp[5 * 16]; int gd[8 * 16]; int gblk[16]; int ng = 0;      // pending problems (v100_pw_wgrad_group's tables), their blocks
-    auto flush_pending = [&](bool grouped) -> int {
+    // Tier 2 (stack_flush_plan2): the narrow blocks' wait in the regions a tier-1 flush has left dead, for one small-tile launch.
+    long long off2[32]; int flush2[32];
+    stack_flush_plan2(blk, n, x16 != nullptr, defer, flush, wg_min_flush_small, off2, flush2);
+    // pending problems of the two tiers (v100_pw_wgrad_group's tables), their blocks
+    struct Pending { const void* gp[5 * 16]; int gd[8 * 16]; int gblk[16]; int ng; } pend[2];
+    pend[0].ng = pend[1].ng = 0;
+    auto flush_pending = [&](int tier, bool grouped) -> int {
+        Pending& q = pend[tier];
+        const void* const* gp = q.gp; const int* gd = q.gd; const int* gblk = q.gblk; int& ng = q.ng;
         int rc = V100_OK;
-        if (grouped) rc = v100_pw_wgrad_group(ng, gp, gd, stream);
+        if (grouped) rc = tier ? v100_pw_wgrad_group_small(ng, gp, gd, stream) : v100_pw_wgrad_group(ng, gp, gd, stream);
         else
             for (int j = 0; j < ng && rc == V100_OK; ++j) {                 // too few tiles: split-K per problem, slabs in the shared workspace
                 IrBwdWs w;
@@ -645,7 +745,8 @@ extern "C" int v100_ir_stack_bwd(const int* desc, const void* const* params, con
     for (int i = n - 1; i >= 0; --i) {
         const StackBlock& b = blk[i];
         IrShape s = b.s;
-        s.defer = defer[i];
+        const int tier = defer[i] ? 0 : off2[i] >= 0 ? 1 : -1;      // whose launch the block's two 1x1 weight gradients wait for
+        s.defer = tier >= 0;
         // dx of block i is dy of block i - 1: 16-bit when both are capable blocks (with or without a residual)
         const bool dx_is16 = i > 0 && grad16_ok(i) && grad16_ok(i - 1);
         if (dy_is16 && !grad16_ok(i)) return V100_ERR_SHAPE;      // (cannot happen: dy_is16 was decided with this block's capability)
@@ -655,23 +756,25 @@ extern "C" int v100_ir_stack_bwd(const int* desc, const void* const* params, con
         const IrParams p = ir_params(params + 18 * i);
         const void* x16i = i > 0 ? (blk[i - 1].y16 >= 0 ? (const void*)(base + blk[i - 1].y16) : nullptr) : x16;
         IrBwdArgs a{i > 0 ? at(blk[i - 1].y) : (const float*)x, at(b.a1), at(b.a2), at(b.a3), p.w1, p.wd, p.w3, p.bn1.gamma, p.bn2.gamma, p.bn3.gamma,
-                    at(b.coef), (const float*)dyi, (float*)dxi, {}, w0, (void*)(base + b.prep), x16i, defer[i] ? w0 + b.defer_off : nullptr};
+                    at(b.coef), (const float*)dyi, (float*)dxi, {}, w0, (void*)(base + b.prep), x16i, tier >= 0 ? w0 + (tier ? off2[i] : b.defer_off) : nullptr};
         ir_grads_carve(s, (float*)grads + goff, a.g);
         CK(ir_bwd(s, a, (hipStream_t)stream));
-        if (defer[i]) {
+        if (tier >= 0) {
             const IrBnCoef bn2 = ir_coef(a.coef, s.mc).bn2;
-            char* own = w0 + b.defer_off;
+            char* own = (char*)a.defer_region;
+            Pending& q = pend[tier];
             // project gradient: dW3 = da3 x relu6(s2 a2 + t2); expand gradient: dW1 = da1 x (shadow of the block input)
             const void* pr[2][5] = {{own, a.a2, bn2.s, bn2.t, a.g.dW3}, {own + ir_defer_da3_bytes(s), a.x16, nullptr, nullptr, a.g.dW1}};
             const int dm[2][8] = {{s.B, s.cout, s.hid, s.T, v100_pw_wgrad_splits(s.B, s.cout, s.hid), 0, 1, WG_IO_G | WG_IO_X},
                                   {s.B, s.hid, s.cin, s.T, v100_pw_wgrad_splits(s.B, s.hid, s.cin), 0, 0, WG_IO_G | WG_IO_X}};
-            for (int j = 0; j < 2; ++j, ++ng) {
-                for (int e = 0; e < 5; ++e) gp[5 * ng + e] = pr[j][e];
-                for (int e = 0; e < 8; ++e) gd[8 * ng + e] = dm[j][e];
-                gblk[ng] = i;
+            for (int j = 0; j < 2; ++j, ++q.ng) {
+                for (int e = 0; e < 5; ++e) q.gp[5 * q.ng + e] = pr[j][e];
+                for (int e = 0; e < 8; ++e) q.gd[8 * q.ng + e] = dm[j][e];
+                q.gblk[q.ng] = i;
             }
         }
-        if (flush[i]) CK(flush_pending(flush[i] > 0));
+        if (flush[i]) CK(flush_pending(0, flush[i] > 0));
+        if (flush2[i]) CK(flush_pending(1, flush2[i] > 0));
         dyi = dxi;
         dy_is16 = dx_is16;
     }

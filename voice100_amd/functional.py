@@ -375,6 +375,12 @@ def set_wgrad_group_thresholds(min_problem_tiles: int = 32, min_flush_tiles: int
     _STACK_PLANS.clear()
 
 
+def set_wgrad_group2_threshold(min_flush_small: int = 96) -> None:
+    """Least workgroups of a tier-2 flush (the narrow blocks' 1x1 weight gradients, parked in the regions a tier-1 flush left dead)
+    that go in one small-tile launch (v100_ir_stack_wgrad_group2_threshold); 0 turns tier 2 off.  Plans no bytes."""
+    N.call("v100_ir_stack_wgrad_group2_threshold", int(min_flush_small))
+
+
 def _stack_plan(cfgs, B, T, bf16, level, last_shadow):
     """(desc ctypes array, per-block offsets, totals) of a run of blocks at this input shape: computed once per distinct key."""
     key = (cfgs, B, T, bf16, level, last_shadow)
