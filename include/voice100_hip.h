@@ -426,7 +426,7 @@ int v100_grad_clip(const void* chunks, int nchunks, const void* grads, int clip_
 
 /* ---- K10 log_softmax + CTC (asr.py:148-152: F.log_softmax(-1) then nn.CTCLoss(blank, 'mean', zero_infinity=True)) --
  * logits [B][T][V] fp32, targets [B][Lmax] int64, in_len / tgt_len [B] int32 (device).  Writes nll[b] =
- * -log p(target_b | logits_b) (inf when infeasible) and grad[b][t][c] = d nll_b / d logits[b][t][c] (zero for
+ * -log p(target_b | logits_b) (inf when infeasible; 0 for a row with no frame and no label) and grad[b][t][c] = d nll_b / d logits[b][t][c] (zero for
  * padded frames and infeasible utterances); the caller forms mean_b(nll_b / tgt_len_b) and scales grad.
  * workspace: v100_ctc_workspace_floats(B, T, Lmax) floats.  Limits: V <= 128, Lmax <= 2047
  * (256 threads x up to 16 lattice states each).  Labels outside [0, V) are treated as blank (the host wrapper can validate

@@ -66,7 +66,8 @@ __global__ __launch_bounds__(256) void ctc_lattice_kernel(const float* __restric
     // guard cells (index 0,1 and S+2,S+3 of the padded row) stay -inf
     for (int i = tid; i < 2 * rs; i += 256) row[i] = NEG_INF;
     __syncthreads();
-    if (Tb <= 0) { if (dir == 0 && tid == 0) nll[b] = INFINITY; return; }
+    // no frame: only an empty transcript has an alignment (the empty one, probability 1), as in nn.CTCLoss
+    if (Tb <= 0) { if (dir == 0 && tid == 0) nll[b] = L <= 0 ? 0.f : INFINITY; return; }
 
     // states handled by this thread: s = tid, tid + 256, ... ; class and skip permission per state
     int cls[NS]; bool skip[NS];
@@ -173,7 +174,8 @@ __global__ __launch_bounds__(1024) void ctc_lattice_skew_kernel(const float* __r
     if (lane == 0) progress[w] = -1;
     if (tid < 2) fin[tid] = NEG_INF;
     __syncthreads();
-    if (Tb <= 0) { if (dir == 0 && tid == 0) nll[b] = INFINITY; return; }
+    // no frame: only an empty transcript has an alignment (the empty one, probability 1), as in nn.CTCLoss
+    if (Tb <= 0) { if (dir == 0 && tid == 0) nll[b] = L <= 0 ? 0.f : INFINITY; return; }
 
     const int u = tid;                                   // state in direction order
     const int sidx = dir == 0 ? u : S - 1 - u;           // lattice state
@@ -447,11 +449,16 @@ static int ctc_run(const float* logits, const long long* targets, const int* in_
     float* lse = beta + (size_t)B * T * Smax;
     const long rows = (long)B * T;
     int* stall = (int*)(lse + (size_t)B * T);
-    V100_GGL(ctc_lse_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, logits, lse, rows, V, stall, B);
     const size_t shmem = (size_t)(CTC_CHUNK * V + 2 * (Smax + 4)) * sizeof(float);
+    // above 64 KiB of dynamic LDS (V = 128 with Lmax 2046 / 2047 only) the launch has to be granted first; a device that refuses
+    // ends the call here, before anything is launched, instead of failing the lattice launch and running the gradient on garbage
+    if (Smax > 2048 && shmem > 65536 &&
+        hipFuncSetAttribute((const void*)ctc_lattice_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem) != hipSuccess) {
+        (void)hipGetLastError();
+        return V100_ERR_LAUNCH;
+    }
+    V100_GGL(ctc_lse_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, logits, lse, rows, V, stall, B);
 #define CTC_LATTICE(NS_)                                                                                                          \
-    if (shmem > 65536)                                                                                                            \
-        (void)hipFuncSetAttribute((const void*)ctc_lattice_kernel<NS_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);       \
     V100_GGL(ctc_lattice_kernel<NS_>, dim3(B, 2), dim3(256), shmem, st, logits, lse, targets, in_len, tgt_len, alpha, beta, \
                        nll, T, V, Lmax, Smax, blank)
     if (Smax <= 1024) {
