@@ -442,6 +442,14 @@ int v100_ctc_loss(const float* logits, const long long* targets, const int* in_l
  * the reference transposes the logits FROM (asr.py:114), so the backward of that transpose needs no pass over the gradient. */
 int v100_ctc_loss_mean_t(const float* logits, const long long* targets, const int* in_len, const int* tgt_len, float* workspace,
                          float* nll, float* loss, float* grad, int grad_bvt, int B, int T, int V, int Lmax, int blank, void* stream);
+/* Up to 1024 lattice states (Lmax <= 511) the lattice runs as a wave pipeline whose neighbouring waves hand edge states over either
+ * once per frame or once per group of frames; a host rule on T and the wave count picks (csrc/ctc.hip), and both give the same bits.
+ * v100_ctc_lattice_plan (HOST only, no GPU call): what the rule picks at this shape: -1 not the pipeline, 0 per frame, else the
+ * group's frames.  v100_ctc_lattice_ring_frames(): frames a wave of the grouped form can run ahead of its neighbour (lengths beyond
+ * it wrap the hand-over ring).  Test hook v100_ctc_lattice_form: force a form process-wide: 0 per frame, 1 grouped, -1 the rule. */
+int v100_ctc_lattice_plan(int T, int Lmax);
+int v100_ctc_lattice_ring_frames(void);
+int v100_ctc_lattice_form(int form);
 
 /* ---- block executor (csrc/block.hip): the whole kernel chain of one InvertedResidual block (asr.py:40-59) per call.
  * shape = {B, Cin, hid, Cout, T, K, stride, residual, bf16, flags, act16} (11 ints; act16: see "act16" above -- then the

@@ -132,8 +132,8 @@ __global__ __launch_bounds__(256) void ctc_lattice_kernel(const float* __restric
 // The same lattice as a WAVE PIPELINE (2 * Lmax + 1 <= 1024 states).  The kernel above pays, on every one of the T dependent
 // frames, an LDS write -> barrier -> LDS read round trip of the whole row across 4 waves (~0.33 us per frame: 170 us at
 // T' = 512).  Here a lane owns ONE state in direction order (u = s for alpha, u = S-1-s for beta, so both recursions read
-// u, u-1, u-2), keeps it in a register and gets its neighbours by DPP (wave_shr:1); only the two states at a wave's upper edge
-// go through LDS, into a ring slot per frame, and the waves run SKEWED: wave w may start frame q as soon as wave w-1 has
+// u, u-1, u-2), keeps it in a register and gets its neighbours by DPP (wave_shr:1); only the state at a wave's upper edge
+// goes through LDS, into a ring slot per frame, and the waves run SKEWED: wave w may start frame q as soon as wave w-1 has
 // published frame q-1 (a progress word per wave; no workgroup barrier in the recursion).  Emission log-probabilities are
 // gathered straight from global memory eight frames ahead.
 // (Round 5, measured at B = 32, T' = 512, 100-token targets, whole head 134 us: timing-only ablations put 62 us on the
@@ -150,16 +150,37 @@ __device__ __forceinline__ float ctc_lse3_log2(float a, float b, float c) {
 #define CTC_RING 32
 #define CTC_SPIN_MAX (1 << 20)      /* a wave never waits forever on a neighbour (all waves of a workgroup are resident: this bound is never reached) */
 #define CTC_PF 8
+// GROUPED hand-over (G > 0 below).  The handshake above is paid on every frame: a progress test, a speculative progress load and edge
+// load, a one-lane store and a one-lane publish under two exec masks, a back-pressure test -- more instructions on the per-frame
+// chain than the recursion itself (two DPP moves, one ctc_lse3_log2, a select, a store).  In the grouped form the unit of exchange
+// between neighbouring waves is a group of G frames, the group in which emissions are prefetched: per group a wave waits ONCE for
+// its upstream wave's group, reads the G edge values with wide LDS reads, runs G frames of pure recursion (no LDS traffic, no
+// polling, no exec-mask change) and hands its own G edge values down with one store and one publish.  Wave w then runs one GROUP
+// behind wave w-1: the pipeline fills in (waves - 1) * G frames instead of (waves - 1), which short inputs on many waves do not earn
+// back -- ctc_lattice_grouped() below is the host's rule.  Every state of every frame sees the same DPP neighbours, the same
+// ctc_lse3_log2, the same emission and the same store in both forms: they agree bit for bit (tests/test_gpu_ctc_group.py).
+// Only ONE edge value crosses a wave boundary in either form: lane 0 of a wave (u = 64 w, even) holds a blank in both directions, a
+// blank has no skip transition, so its u-2 neighbour is never consumed; lane 1's u-2 is lane 0's u-1, which the first DPP delivers.
+#ifndef CTC_GROUP
+#define CTC_GROUP 16                /* 4 and 8 were built and measured: DESIGN_rejected.md, profiles/ctc_group_ab.txt */
+#endif
+#define CTC_GRING 8                 /* groups per ring */
+static_assert(CTC_GROUP % 4 == 0 && CTC_GROUP >= 4 && CTC_GROUP <= 16, "the group's edge values travel as float4");
+typedef float ctc_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float ctc_wave_shr1(float fill, float v) {       // lane l gets v of lane l-1; lane 0 gets `fill`
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
 }
 
+// G = 0: the per-frame hand-over, emissions prefetched CTC_PF frames ahead; G > 0: the grouped hand-over, groups (and prefetch) of G frames
+template <int G>
 __global__ __launch_bounds__(1024) void ctc_lattice_skew_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
                                                                 const long long* __restrict__ targets, const int* __restrict__ in_len,
                                                                 const int* __restrict__ tgt_len, float* __restrict__ alpha,
                                                                 float* __restrict__ beta, float* __restrict__ nll, int T, int V, int Lmax,
                                                                 int Smax, int blank, int* __restrict__ stall) {
-    __shared__ float bnd[16][CTC_RING][2];
+    constexpr int PF = G > 0 ? G : CTC_PF;                                  // frames per prefetch group
+    // per upstream wave a ring of the top state's values: one slot per frame, or one slot of G frames per group
+    __shared__ __attribute__((aligned(16))) float bnd[16][G > 0 ? CTC_GRING * G : CTC_RING];
     __shared__ int progress[16];
     __shared__ float fin[2];
     const int b = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x;
@@ -197,32 +218,46 @@ __global__ __launch_bounds__(1024) void ctc_lattice_skew_kernel(const float* __r
         const int t = dir == 0 ? qq : Tb - 1 - qq;
         return (lg[(size_t)t * V] - ls[t]) * 1.44269504088896340736f;       // log2 units: the recursion runs on exp2 / log2 directly
     };
-    float cur[CTC_PF], nxt[CTC_PF];
+    // a group's emissions become opaque where the group starts to use them (not where they are loaded: that would wait for the
+    // loads on the spot): a rounded product in every frame of both forms, never contracted into the frame's add
+    auto settle = [](float (&e)[PF]) {
 #pragma unroll
-    for (int j = 0; j < CTC_PF; ++j) cur[j] = emission(j);
+        for (int j = 0; j < PF; ++j) asm volatile("" : "+v"(e[j]));
+    };
+    float cur[PF], nxt[PF];
+#pragma unroll
+    for (int j = 0; j < PF; ++j) cur[j] = emission(j);
+    settle(cur);
 
     // relaxed workgroup-scope atomics: plain ds_read / ds_write that the compiler neither caches nor fences (a `volatile` access
     // is bracketed by vmcnt(0) waits, i.e. by the acknowledgement of the previous frame's lattice store: 240 us instead of 170).
     // LDS executes one wave's operations in order, so "edge values, then progress word" needs no fence -- only program order.
     auto prog_load = [&](int i) { return __hip_atomic_load(&progress[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
     float a_prev = NEG_INF;
-    int pnext = -2;
-    float n63 = NEG_INF, n62 = NEG_INF;
     // lattice row pointer of frame q, advanced by one row per frame (alpha walks up, beta down)
     float* lrow = lat + (size_t)(dir == 0 ? 0 : Tb - 1) * Smax + sidx;
     const long lstep = dir == 0 ? (long)Smax : -(long)Smax;
-    // one frame; UP: there is an upstream wave (w > 0), DOWN: a downstream wave (w < NW - 1), FIRST: q == 0.  The roles are fixed
-    // per wave, so the loop below is instantiated per role instead of testing them on every frame.
+    // the recursion of one frame (not the first); edge: the upstream wave's top state of the previous frame (lane 0's u-1)
+    auto step = [&](float edge, float e) {
+        const float sm1 = ctc_wave_shr1(edge, a_prev);
+        const float sm2 = ctc_wave_shr1(NEG_INF, sm1);      // lane 0's u-2 is never consumed: see above
+        const float v = e + ctc_lse3_log2(a_prev, sm1, skip ? sm2 : NEG_INF);
+        return active ? v : NEG_INF;
+    };
+    int pnext = -2;
+    float n63 = NEG_INF;
+    // PER-FRAME form, one frame; UP: there is an upstream wave (w > 0), DOWN: a downstream wave (w < NW - 1), FIRST: q == 0.  The roles
+    // are fixed per wave, so the loop below is instantiated per role instead of testing them on every frame.
     auto frame = [&](auto up_t, auto down_t, auto first_t, int q, float e) {
         constexpr bool UP = decltype(up_t)::value, DOWN = decltype(down_t)::value, FIRST = decltype(first_t)::value;
-        float v63 = NEG_INF, v62 = NEG_INF;
+        float v63 = NEG_INF;
         if constexpr (UP) {
             if constexpr (!FIRST) {
                 // (the progress word travels as an opaque VGPR until here: as a plain uniform value hipcc moves it to an SGPR --
                 //  and waits for the LDS read -- right where it was issued, which puts the read's latency back on the chain)
                 asm volatile("" : "+v"(pnext));
                 if (__builtin_amdgcn_readfirstlane(pnext) >= q - 1) {    // the copy fetched during the previous frame is valid
-                    v63 = n63; v62 = n62;
+                    v63 = n63;
                 } else {
                     // wait until the upstream wave is TWO frames ahead (or done): with a skew of one, the speculative fetch
                     // below would find frame q unpublished on every frame and this slow path would run each time
@@ -231,26 +266,18 @@ __global__ __launch_bounds__(1024) void ctc_lattice_skew_kernel(const float* __r
                     for (; prog_load(w - 1) < need && guard < CTC_SPIN_MAX; ++guard) __builtin_amdgcn_s_sleep(1);
                     if (guard >= CTC_SPIN_MAX && lane == 0) stall[b] = 1;      // never reached by design; if it is, poison the result (no silent wrong loss)
                     asm volatile("" ::: "memory");
-                    v63 = bnd[w - 1][(q - 1) & (CTC_RING - 1)][0];
-                    v62 = bnd[w - 1][(q - 1) & (CTC_RING - 1)][1];
+                    v63 = bnd[w - 1][(q - 1) & (CTC_RING - 1)];
                 }
             }
-            // speculative fetch for frame q + 1 (edge values of frame q): progress word FIRST -- if it already says >= q, the slot
+            // speculative fetch for frame q + 1 (edge value of frame q): progress word FIRST -- if it already says >= q, the slot
             // read after it (LDS keeps a wave's operations in order) is complete; used next frame, so its latency hides here
             pnext = prog_load(w - 1);
             asm volatile("" ::: "memory");
-            n63 = bnd[w - 1][q & (CTC_RING - 1)][0];
-            n62 = bnd[w - 1][q & (CTC_RING - 1)][1];
+            n63 = bnd[w - 1][q & (CTC_RING - 1)];
         }
         float v;
-        if constexpr (FIRST) {
-            v = (u <= 1) ? e : NEG_INF;
-        } else {
-            const float sm1 = ctc_wave_shr1(v63, a_prev);
-            const float sm2 = ctc_wave_shr1(v62, sm1);
-            v = e + ctc_lse3_log2(a_prev, sm1, skip ? sm2 : NEG_INF);
-        }
-        if (!active) v = NEG_INF;
+        if constexpr (FIRST) v = (active && u <= 1) ? e : NEG_INF;
+        else v = step(v63, e);
         if constexpr (DOWN) {
             // back-pressure, once per half ring: frames q .. q + RING/2 - 1 reuse the slots of frames q - RING .. q - RING/2 - 1, which
             // wave w+1 has read once it has published frame q - RING/2
@@ -260,7 +287,7 @@ __global__ __launch_bounds__(1024) void ctc_lattice_skew_kernel(const float* __r
                 if (guard >= CTC_SPIN_MAX && lane == 0) stall[b] = 1;
             }
             asm volatile("" ::: "memory");
-            if (lane >= 62) bnd[w][q & (CTC_RING - 1)][63 - lane] = v;
+            if (lane == 63) bnd[w][q & (CTC_RING - 1)] = v;
         }
         asm volatile("" ::: "memory");       // program order only: LDS performs one wave's writes in the order they were issued
         if (lane == 0) __hip_atomic_store(&progress[w], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -268,25 +295,98 @@ __global__ __launch_bounds__(1024) void ctc_lattice_skew_kernel(const float* __r
         if (active) *lrow = v * 0.69314718055994530942f;      // the lattice is stored in natural-log units
         lrow += lstep;
     };
-    auto run = [&](auto up_t, auto down_t) {
-        for (int q0 = 0; q0 < Tb; q0 += CTC_PF) {
+    // GROUPED form, one group of G frames starting at q0 = g * G (n of them exist; FULL: n == G and g > 0).  progress[w] is the last
+    // GROUP wave w has published (-1: none).  Slot g & (GRING - 1) of wave w's ring holds what wave w+1 needs for ITS group g: wave
+    // w's top state of frames q0 - 1 .. q0 + G - 2, i.e. the value it carried into the group and its first G - 1 results (the last
+    // result rides in the next group's slot; frame 0 reads no neighbour, so slot 0's first value is never used).
+    auto group = [&](auto up_t, auto down_t, auto full_t, int g, int n) {
+        constexpr bool UP = decltype(up_t)::value, DOWN = decltype(down_t)::value, FULL = decltype(full_t)::value;
+        constexpr int G4 = G / 4;
+        ctc_f4 edge[G4 > 0 ? G4 : 1];
+        for (int i = 0; i < G4; ++i) edge[i] = ctc_f4{NEG_INF, NEG_INF, NEG_INF, NEG_INF};
+        if constexpr (UP) {
+            // progress word FIRST, the slot right behind it: if the word already says >= g the slot read after it (LDS keeps a wave's
+            // operations in order) is complete, and the wait cost one LDS round trip per group; else spin, then read the slot again
+            const ctc_f4* slot = reinterpret_cast<const ctc_f4*>(&bnd[w - 1][(g & (CTC_GRING - 1)) * G]);
+            const int p = prog_load(w - 1);
+            asm volatile("" ::: "memory");
 #pragma unroll
-            for (int j = 0; j < CTC_PF; ++j) nxt[j] = emission(q0 + CTC_PF + j);
-            if (q0 == 0) {
+            for (int i = 0; i < G4; ++i) edge[i] = slot[i];
+#pragma unroll
+            for (int i = 0; i < G4; ++i) asm volatile("" : "+v"(edge[i]));      // issued here, ahead of the test: hipcc otherwise sinks the reads behind it
+            if (__builtin_amdgcn_readfirstlane(p) < g) {
+                int guard = 0;
+                for (; prog_load(w - 1) < g && guard < CTC_SPIN_MAX; ++guard) __builtin_amdgcn_s_sleep(1);
+                if (guard >= CTC_SPIN_MAX && lane == 0) stall[b] = 1;      // never reached by design; if it is, poison the result (no silent wrong loss)
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int i = 0; i < G4; ++i) edge[i] = slot[i];
+            }
+        }
+        const float* ev = reinterpret_cast<const float*>(edge);
+        // G frames of pure recursion: no LDS traffic, no polling, no exec-mask change
+        float val[G > 0 ? G : 1];
+        const float carried = a_prev;
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            val[j] = a_prev;                                   // (a frame past the end repeats the last value: never stored, never consumed)
+            if (FULL || j < n) {
+                if (!FULL && g == 0 && j == 0) val[j] = (active && u <= 1) ? cur[0] : NEG_INF;
+                else val[j] = step(ev[j], cur[j]);
+            }
+            asm volatile("" : "+v"(val[j]));                   // the frame is computed here, by all lanes: not sunk under the stores' exec mask
+            a_prev = val[j];
+        }
+        if constexpr (DOWN) {
+            // back-pressure, once per half ring: groups g .. g + GRING/2 - 1 reuse the slots of groups g - GRING .. g - GRING/2 - 1, which
+            // wave w+1 has read (at the start of each of them) once it has published group g - GRING/2
+            if ((g & (CTC_GRING / 2 - 1)) == 0 && g >= CTC_GRING / 2) {
+                int guard = 0;
+                for (; prog_load(w + 1) < g - CTC_GRING / 2 && guard < CTC_SPIN_MAX; ++guard) __builtin_amdgcn_s_sleep(1);
+                if (guard >= CTC_SPIN_MAX && lane == 0) stall[b] = 1;
+            }
+            asm volatile("" ::: "memory");
+            if (lane == 63) {
+                ctc_f4* slot = reinterpret_cast<ctc_f4*>(&bnd[w][(g & (CTC_GRING - 1)) * G]);
+#pragma unroll
+                for (int i = 0; i < G4; ++i)
+                    slot[i] = ctc_f4{i == 0 ? carried : val[4 * i - 1], val[4 * i], val[4 * i + 1], val[4 * i + 2]};
+            }
+        }
+        if constexpr (UP || DOWN) {
+            asm volatile("" ::: "memory");   // program order only: LDS performs one wave's writes in the order they were issued
+            if (lane == 0) __hip_atomic_store(&progress[w], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        if (active) {
+#pragma unroll
+            for (int j = 0; j < G; ++j)
+                if (FULL || j < n) lrow[j * lstep] = val[j] * 0.69314718055994530942f;      // the lattice is stored in natural-log units
+        }
+        lrow += G * lstep;
+    };
+    auto run = [&](auto up_t, auto down_t) {
+        for (int q0 = 0; q0 < Tb; q0 += PF) {
+#pragma unroll
+            for (int j = 0; j < PF; ++j) nxt[j] = emission(q0 + PF + j);
+            if constexpr (G > 0) {
+                if (q0 > 0 && q0 + G <= Tb) group(up_t, down_t, std::true_type{}, q0 / G, G);
+                else group(up_t, down_t, std::false_type{}, q0 / G, min(G, Tb - q0));
+            } else if (q0 == 0) {
                 frame(up_t, down_t, std::true_type{}, 0, cur[0]);
 #pragma unroll
-                for (int j = 1; j < CTC_PF; ++j)
+                for (int j = 1; j < PF; ++j)
                     if (j < Tb) frame(up_t, down_t, std::false_type{}, j, cur[j]);
-            } else if (q0 + CTC_PF <= Tb) {
+            } else if (q0 + PF <= Tb) {
 #pragma unroll
-                for (int j = 0; j < CTC_PF; ++j) frame(up_t, down_t, std::false_type{}, q0 + j, cur[j]);
+                for (int j = 0; j < PF; ++j) frame(up_t, down_t, std::false_type{}, q0 + j, cur[j]);
             } else {
 #pragma unroll
-                for (int j = 0; j < CTC_PF; ++j)
+                for (int j = 0; j < PF; ++j)
                     if (q0 + j < Tb) frame(up_t, down_t, std::false_type{}, q0 + j, cur[j]);
             }
 #pragma unroll
-            for (int j = 0; j < CTC_PF; ++j) cur[j] = nxt[j];
+            for (int j = 0; j < PF; ++j) cur[j] = nxt[j];
+            settle(cur);
         }
     };
     const bool has_up = w > 0, has_down = w < NW - 1;
@@ -413,6 +513,34 @@ extern "C" int v100_ctc_workspace_floats(int B, int T, int Lmax) {      // alpha
     return n > 0x7fffffffL ? -1 : (int)n;
 }
 
+// Which hand-over the wave pipeline runs (host rule).  The grouped form saves time on every frame and pays a longer pipeline fill, a
+// group instead of a frame per downstream wave, so it runs from a padded length T on that grows with the wave count nw:
+// T >= 32 + 4 nw.  Measured, not derived: tools/micro/ctc_group_sweep.py times both forms over T x waves (profiles/
+// ctc_group_ab.txt: with groups of 16 the grouped form wins from T = 32 / 32 / 32 / 48 / 96 on 1 / 2 / 4 / 8 / 16 waves, the rule
+// asks for 36 / 40 / 48 / 64 / 96; around those lengths the two are within 1 - 2 us of each other, further down the per-frame form
+// wins by up to 9 us).  Rows whose in_len is shorter than T finish early in either form.
+static int ctc_lattice_form = -1;       // test hook: -1 the rule, 0 per frame, 1 grouped
+static bool ctc_lattice_rule(int T, int nw) { return T >= 32 + 4 * nw; }
+static bool ctc_lattice_grouped(int T, int nw) { return ctc_lattice_form >= 0 ? ctc_lattice_form != 0 : ctc_lattice_rule(T, nw); }
+
+// Test hook: force the wave pipeline's hand-over process-wide: 0 per frame, 1 grouped, -1 back to the rule.
+extern "C" int v100_ctc_lattice_form(int form) {
+    if (form < -1 || form > 1) return V100_ERR_SHAPE;
+    ctc_lattice_form = form;
+    return V100_OK;
+}
+
+// Host only (no GPU call): what ctc_run launches for the lattice at this shape, whatever the hook says: -1 the barrier kernels
+// (more than 1024 states), 0 the pipeline with the per-frame hand-over, else the pipeline with groups of that many frames.
+extern "C" int v100_ctc_lattice_plan(int T, int Lmax) {
+    const int Smax = 2 * Lmax + 1;
+    if (T <= 0 || Lmax < 0 || Smax > 1024) return -1;
+    return ctc_lattice_rule(T, (Smax + 63) / 64) ? CTC_GROUP : 0;
+}
+
+// Frames a wave of the grouped pipeline can run ahead of its downstream wave: the ring's capacity.
+extern "C" int v100_ctc_lattice_ring_frames(void) { return CTC_GRING * CTC_GROUP; }
+
 static int ctc_run(const float* logits, const long long* targets, const int* in_len, const int* tgt_len, float* workspace, float* nll,
                    float* loss, float* grad, int grad_bvt, int B, int T, int V, int Lmax, int blank, void* stream);
 
@@ -463,8 +591,12 @@ static int ctc_run(const float* logits, const long long* targets, const int* in_
                        nll, T, V, Lmax, Smax, blank)
     if (Smax <= 1024) {
         const int nw = (Smax + 63) / 64;
-        V100_GGL(ctc_lattice_skew_kernel, dim3(B, 2), dim3(64 * nw), 0, st, logits, lse, targets, in_len, tgt_len, alpha, beta,
-                           nll, T, V, Lmax, Smax, blank, stall);
+        if (ctc_lattice_grouped(T, nw))
+            V100_GGL(ctc_lattice_skew_kernel<CTC_GROUP>, dim3(B, 2), dim3(64 * nw), 0, st, logits, lse, targets, in_len, tgt_len, alpha,
+                     beta, nll, T, V, Lmax, Smax, blank, stall);
+        else
+            V100_GGL(ctc_lattice_skew_kernel<0>, dim3(B, 2), dim3(64 * nw), 0, st, logits, lse, targets, in_len, tgt_len, alpha, beta,
+                     nll, T, V, Lmax, Smax, blank, stall);
     } else if (Smax <= 2048) { CTC_LATTICE(8); }
     else { CTC_LATTICE(16); }
 #undef CTC_LATTICE
