@@ -326,18 +326,21 @@ int v100_pw_gemm_io(const void* A_bf16, const void* X, const void* X2, const flo
 int v100_pw_wgrad_io(const void* G, const void* G2, const float* ga, const float* gb, const float* gc, int g_mode,
                      const void* X, const float* xa, const float* xb, int x_mode, float* partial, float* dW, int S, int B,
                      int M, int K, int T, int io16, void* stream);
-/* Several such weight gradients in ONE launch (csrc/pointwise_bf16_wgrad_group.h), each workgroup carrying one tile through the
- * whole contraction: no split-K slabs, no reduce launch.  The workgroup walks the contraction in the order of the S splits of
- * v100_pw_wgrad_io and sums their partial tiles in slab order, so every dW equals v100_pw_wgrad_io(..., S, ...) bit for bit.
+/* Several such weight gradients in ONE launch (csrc/wgrad_group.h, csrc/pointwise_bf16_group.hip), each workgroup carrying one
+ * tile through the whole contraction: no split-K slabs, no reduce launch.  The workgroup walks the contraction in the order of the S
+ * splits of v100_pw_wgrad_io and sums their partial tiles in slab order, so every dW equals v100_pw_wgrad_io(..., S, ...) bit for bit.
  * Only the two finished-gradient forms of the InvertedResidual backward (asr.py:45-59; csrc/block.hip v100_ir_stack_bwd): g_mode 0,
- * io16 = 1 | 4, x_mode 1 (project: M % 256 == 0, K % 128 == 0) or 0 (expand on da1: M % 128 == 0, K % 256 == 0), any S that takes.
+ * io16 = 1 | 4, x_mode 1 (project) or 0 (expand on da1), any S that takes.
+ * A TIER is a tile shape with its kernel; the two tiers share eligibility, placement and launch, and differ in nothing else.
+ * The wide tier (these three; csrc/pointwise_bf16_wgrad_group.h): project M % 256 == 0, K % 128 == 0; expand M % 128 == 0, K % 256 == 0.
  * n <= 16 problems; ptrs (HOST, 5 per problem): G X xa xb dW; dims (HOST, 8 per problem): B M K T S g_mode x_mode io16.
- * _supported: 1 when a problem qualifies (anything else makes v100_pw_wgrad_group return 1); _tiles: its workgroups. */
+ * Status: 3 for NULL tables, 1 for n outside 1..16, then per problem 3 for a NULL operand before 1 for one that does not qualify.
+ * _supported: 1 when a problem qualifies; _tiles: its workgroups (0: not whole tiles). */
 int v100_pw_wgrad_group_supported(int B, int M, int K, int T, int S, int g_mode, int x_mode, int io16);
 int v100_pw_wgrad_group_tiles(int M, int K, int x_mode);
 int v100_pw_wgrad_group(int n, const void* const* ptrs, const int* dims, void* stream);
-/* The same launch on 128 x 128 tiles (csrc/pointwise_bf16_wgrad_small.h), for gradients with too few of the tiles above to fill the
- * chip (256 x 1024: 8 of those, 16 of these): both x_modes with M % 128 == 0 and K % 128 == 0, same tables, same bit-identity. */
+/* The small tier (csrc/pointwise_bf16_wgrad_small.h): 128 x 128 tiles, for gradients with too few of the tiles above to fill the
+ * chip (256 x 1024: 8 of those, 16 of these): both x_modes with M % 128 == 0 and K % 128 == 0, same tables, status and bit-identity. */
 int v100_pw_wgrad_group_small_supported(int B, int M, int K, int T, int S, int g_mode, int x_mode, int io16);
 int v100_pw_wgrad_group_small_tiles(int M, int K, int x_mode);
 int v100_pw_wgrad_group_small(int n, const void* const* ptrs, const int* dims, void* stream);

@@ -32,6 +32,17 @@ def test_every_declared_symbol_is_exported(lib):
     assert set(N.parse_header()) == set(declared)
 
 
+def test_restype_is_the_declared_return_type(lib):
+    """every prototype of the header: the loaded function returns c_longlong exactly where the header says `long long`"""
+    from voice100_amd import _native as N
+    text = re.sub(r"/\*.*?\*/", "", open(N.HEADER_PATH).read(), flags=re.S)
+    declared = dict((name, ty) for ty, name in re.findall(r"\b(\w+)\s+(v100_\w+)\s*\(", text))
+    assert set(declared) == set(N.parse_header()) and set(declared.values()) == {"int", "long"}      # (`long long name(`: the word before the name)
+    for name, ty in declared.items():
+        assert getattr(lib, name).restype is (ctypes.c_longlong if ty == "long" else ctypes.c_int), name
+    assert lib.v100_ir_stack_plan.restype is ctypes.c_longlong and lib.v100_ir_stack_bwd.restype is ctypes.c_int
+
+
 def test_host_helpers_need_no_gpu(lib):
     assert lib.v100_pw_num_parts(32, 1024) == 32 * 8
     assert lib.v100_dw_num_groups(32, 2048) == 1 and lib.v100_dw_num_groups(32, 256) == 8 and lib.v100_dw_num_groups(2, 4) == 2

@@ -89,6 +89,19 @@ def test_group_equals_per_problem_and_float64(cuda, idx):
         close(got, p["ref"], f"grouped wgrad {spec}", tol=WGRAD_TOL)
 
 
+def test_full_list_of_mixed_tile_counts_fills_every_xcd(cuda):
+    """WG_GROUP_MAX = 16 problems, B = 3: eight project gradients of 256 x 128 and 512 x 128 (one and two tiles), eight expand
+    gradients of 128 x 256 and 128 x 512, the modes alternating, S = the library's own, B, 2 and 1.  24 tiles: three slots on every
+    XCD, so a problem's slot0 is past 0 on each.  T = 72 (the tail kernel), then T = 64 (the kernel without the masks)."""
+    for T in (72, 64):
+        specs = [(mode, 3, M, K, T, S) for S in (None, 3, 2, 1) for M2 in (1, 2)
+                 for mode, M, K in ((PROJECT, 256 * M2, 128), (EXPAND, 128, 256 * M2))]
+        assert len(specs) == 16
+        probs = [_problem(cuda, *p) for p in specs]
+        for p, got, spec in zip(probs, _run_group(cuda, probs), specs):
+            assert torch.equal(got, p["want"]), spec
+
+
 def test_ineligible_problems_are_refused(cuda):
     N = _native()
     ok = lambda *a: N.helper("v100_pw_wgrad_group_supported", *a)

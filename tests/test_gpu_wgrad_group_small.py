@@ -78,6 +78,17 @@ def test_small_group_equals_per_problem_and_float64(cuda, idx):
         close(got, p["ref"], f"small grouped wgrad {spec}", tol=WGRAD_TOL)
 
 
+def test_full_list_of_mixed_tile_counts_fills_every_xcd(cuda):
+    """WG_GROUP_MAX = 16 problems, B = 3: 128 x 128 and 256 x 128 (one and two tiles) in both modes, alternating, S = the library's
+    own, B, 2 and 1.  24 tiles: three slots on every XCD.  T = 72 (the tail kernel), then T = 64 (the kernel without the masks)."""
+    for T in (72, 64):
+        specs = [(mode, 3, M, 128, T, S) for S in (None, 3, 2, 1) for M in (128, 256) for mode in (PROJECT, EXPAND)]
+        assert len(specs) == 16
+        probs = [_problem(cuda, *p) for p in specs]
+        for p, got, spec in zip(probs, _run_small(cuda, probs), specs):
+            assert torch.equal(got, p["want"]), spec
+
+
 def test_ineligible_problems_are_refused(cuda):
     N = _native()
     ok = lambda *a: N.helper("v100_pw_wgrad_group_small_supported", *a)

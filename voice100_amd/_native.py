@@ -30,14 +30,19 @@ _protos = None
 STATUS = {1: "invalid or unsupported shape/mode", 2: "kernel launch error", 3: "required pointer is NULL"}
 
 
+class Proto(list):
+    """[(ctype, argname), ...] of a prototype, and its declared return type in `restype`."""
+
+
 def parse_header(path=HEADER_PATH):
-    """{name: [(ctype, argname), ...]} for every `int v100_*(...)` prototype in the header."""
+    """{name: Proto} for every `int` / `long long v100_*(...)` prototype in the header."""
     text = open(path).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     protos = {}
-    for m in re.finditer(r"\b(?:int|long long)\s+(v100_\w+)\s*\(([^)]*)\)\s*;", text):
-        name, args = m.group(1), m.group(2)
-        params = []
+    for m in re.finditer(r"\b(int|long long)\s+(v100_\w+)\s*\(([^)]*)\)\s*;", text):
+        name, args = m.group(2), m.group(3)
+        params = Proto()
+        params.restype = _CTYPES[m.group(1)]
         for a in args.split(","):
             a = " ".join(a.split())
             if not a or a == "void":
@@ -68,7 +73,7 @@ def load():
         for name, params in protos.items():
             fn = getattr(lib, name)        # AttributeError if the header declares a symbol the .so lacks
             fn.argtypes = [t for t, _ in params]
-            fn.restype = ctypes.c_longlong if (name.endswith("_bytes") or name in ("v100_launch_count", "v100_ir_stack_plan", "v100_world_randn_bound", "v100_resample_out_len")) else ctypes.c_int
+            fn.restype = params.restype
         _lib, _protos = lib, protos
         return lib
 

@@ -8,6 +8,7 @@
 #include "../../include/voice100_hip.h"
 #include "depthwise_common.h"   // DwFin / DwPre: BatchNorm finalisation inside the producing / the consuming kernel
 #include "block_shape.h"
+#include "wgrad_group.h"
 #include <algorithm>
 // With one depthwise group the depthwise kernels finalise the BatchNorms on both of their sides (forward BatchNorm 1 from the expand
 // GEMM's slab, backward BatchNorm-2 backward from the project backward-data GEMM's slab): bit-identical results, 16 launches fewer,
@@ -188,32 +189,36 @@ static size_t ir_bwd_carve(const IrShape& s, void* base, IrBwdWs& w) {
 // block's coefficient blob) -- nothing the rest of the backward walk overwrites.
 static size_t ir_defer_da3_bytes(const IrShape& s) { return al256((size_t)s.B * s.cout * pitch16(s.T2, s.B) * 2); }
 static size_t ir_defer_bytes(const IrShape& s) { return ir_defer_da3_bytes(s) + al256((size_t)s.B * s.hid * pitch16(s.T, s.B) * 2); }
-static int ir_wgrad_defer_tiles(const IrShape& s) {      // of both gradients
-    return v100_pw_wgrad_group_tiles(s.cout, s.hid, 1) + v100_pw_wgrad_group_tiles(s.hid, s.cin, 0);
-}
 // (what decides that ir_bwd has finished da3 / da1 to park: everything but the gradients' tiles)
 static bool ir_wgrad_defer_path(const IrShape& s, bool have_x16) {
     const int B = s.B, hid = s.hid, T = s.T, K = s.K;
     if (s.act16 < 4 || !s.shadows || s.frozen || !have_x16 || s.S != 1) return false;
     return ir_act16_supported(s) && v100_dw_num_groups(B, hid) == 1 && dw_bwd_da1_supported(B, hid, T, K, 1);
 }
-static bool ir_wgrad_defer_ok(const IrShape& s, bool have_x16, int min_tiles) {
-    const int B = s.B, cin = s.cin, hid = s.hid, cout = s.cout, T = s.T;
+// THE two problems of a deferring block: q[0] the project gradient dW3 = da3 x relu6(s2 a2 + t2), q[1] the expand gradient
+// dW1 = da1 x (shadow of the block input).  a NULL: the shapes alone (eligibility, tile counts)
+static void ir_wgrad_problems(const IrShape& s, const IrBwdArgs* a, WgGroupProblem q[2]) {
+    q[0] = WgGroupProblem{nullptr, nullptr, nullptr, nullptr, nullptr, s.B, s.cout, s.hid, s.T, v100_pw_wgrad_splits(s.B, s.cout, s.hid), 1, 0, 0, 0};
+    q[1] = WgGroupProblem{nullptr, nullptr, nullptr, nullptr, nullptr, s.B, s.hid, s.cin, s.T, v100_pw_wgrad_splits(s.B, s.hid, s.cin), 0, 0, 0, 0};
+    if (!a) return;
+    const IrBnCoef bn2 = ir_coef(a->coef, s.mc).bn2;
+    q[0].G = a->defer_region; q[0].X = a->a2; q[0].xa = bn2.s; q[0].xb = bn2.t; q[0].dW = a->g.dW3;
+    q[1].G = (char*)a->defer_region + ir_defer_da3_bytes(s); q[1].X = a->x16; q[1].dW = a->g.dW1;
+}
+static int ir_wgrad_defer_tiles(const IrShape& s, WgTier tier) {      // of both gradients
+    WgGroupProblem q[2];
+    ir_wgrad_problems(s, nullptr, q);
+    return pw_wgrad_group_tiles(tier, q[0].M, q[0].K, q[0].x_mode) + pw_wgrad_group_tiles(tier, q[1].M, q[1].K, q[1].x_mode);
+}
+// both gradients are problems of the tier's launch, of at least min_tiles tiles each (tier 2 has no minimum: it takes what is
+// below tier 1's)
+static bool ir_wgrad_defer_ok(const IrShape& s, bool have_x16, WgTier tier, int min_tiles) {
     if (!ir_wgrad_defer_path(s, have_x16)) return false;
-    const int io = WG_IO_G | WG_IO_X;
-    return v100_pw_wgrad_group_supported(B, cout, hid, T, v100_pw_wgrad_splits(B, cout, hid), 0, 1, io) &&
-           v100_pw_wgrad_group_supported(B, hid, cin, T, v100_pw_wgrad_splits(B, hid, cin), 0, 0, io) &&
-           v100_pw_wgrad_group_tiles(cout, hid, 1) >= min_tiles && v100_pw_wgrad_group_tiles(hid, cin, 0) >= min_tiles;
-}
-// Tier 2: a block below tier 1's tile minimum whose gradients are problems of the 128 x 128 launch (v100_pw_wgrad_group_small)
-static bool ir_wgrad_defer_small_ok(const IrShape& s, bool have_x16) {
-    const int B = s.B, cin = s.cin, hid = s.hid, cout = s.cout, T = s.T, io = WG_IO_G | WG_IO_X;
-    return ir_wgrad_defer_path(s, have_x16) &&
-           v100_pw_wgrad_group_small_supported(B, cout, hid, T, v100_pw_wgrad_splits(B, cout, hid), 0, 1, io) &&
-           v100_pw_wgrad_group_small_supported(B, hid, cin, T, v100_pw_wgrad_splits(B, hid, cin), 0, 0, io);
-}
-static int ir_wgrad_defer_small_tiles(const IrShape& s) {
-    return v100_pw_wgrad_group_small_tiles(s.cout, s.hid, 1) + v100_pw_wgrad_group_small_tiles(s.hid, s.cin, 0);
+    WgGroupProblem q[2];
+    ir_wgrad_problems(s, nullptr, q);
+    for (const WgGroupProblem& p : q)
+        if (!pw_wgrad_group_supported(tier, p) || pw_wgrad_group_tiles(tier, p.M, p.K, p.x_mode) < min_tiles) return false;
+    return true;
 }
 
 extern "C" long long v100_ir_bwd_workspace_bytes(const int* shape) {
@@ -446,19 +451,21 @@ extern "C" int v100_ir_stack_fwd_eval(int n, const int* shapes, const void* cons
 // All activations the run keeps for backward live in ONE caller-allocated blob laid out by v100_ir_stack_plan; backward walks the
 // blocks in reverse with one shared workspace and two ping-pong gradient buffers.  Pure sequencing of ir_fwd_train / ir_bwd
 // (same kernels, same order, bit-identical results) -- except that backward runs the wide blocks' 1x1 weight gradients later, several
-// blocks' in one grouped launch (stack_flush_plan; the same sums in the same order, bit-identical too), and the narrow blocks below
-// them in a second one on smaller tiles (stack_flush_plan2).
+// blocks' in one grouped launch (stack_wgrad_plan; the same sums in the same order, bit-identical too), and the narrow blocks below
+// them in a second one on smaller tiles (tier 2 of the same plan).
 // desc, plan and params: include/voice100_hip.h; the plan ends with {blob_bytes, bwd_ws_bytes, grad_floats, fwd_ws_offset, 0, 0}
 enum { ST_N, ST_B, ST_T, ST_BF16, ST_LEVEL, ST_SHADOW, ST_HDR };
 namespace {
 struct StackBlock { IrShape s; long long a1, a2, a3, y, y16, coef, prep; int Tout; size_t grad_floats; long long defer_off; };
 // bwd_ws = the shared workspace (wsmax: the largest block's), two ping-pong gradient buffers (dxmax each), then the deferring blocks' regions
 struct StackTotals { size_t blob_bytes, bwd_ws, grad_floats, fwd_ws_off, wsmax, dxmax; };
-// the least tiles of a weight gradient that defers to a grouped launch (one XCD's 32 CUs: 8 such problems fill the chip)
-// and of a grouped flush (3/4 of the chip; below, split-K launches per problem are faster); v100_ir_stack_wgrad_group_thresholds
-int wg_min_problem_tiles = 32, wg_min_flush_tiles = 192;
+// the least tiles of a weight gradient that defers to a grouped launch (one XCD's 32 CUs: 8 such problems fill the chip), of a
+// grouped flush (3/4 of the chip; below, split-K launches per problem are faster) and the least workgroups of a tier-2 flush that go
+// in one small-tile launch (0: tier 2 off); v100_ir_stack_wgrad_group_thresholds, v100_ir_stack_wgrad_group2_threshold
+struct WgThresholds { int min_problem_tiles, min_flush_tiles, min_flush_small; };
+WgThresholds wg_thresholds = {32, 192, 96};
 // fills blocks[0..n) and the totals; returns 0 on a bad descriptor
-int stack_layout(const int* desc, StackBlock* blk, StackTotals& t, int min_tiles = wg_min_problem_tiles) {
+int stack_layout(const int* desc, StackBlock* blk, StackTotals& t, int min_tiles = wg_thresholds.min_problem_tiles) {
     t = StackTotals{};
     const int n = desc[ST_N], B = desc[ST_B], bf = desc[ST_BF16], level = desc[ST_LEVEL];
     if (n <= 0 || n > 32 || B <= 0 || desc[ST_T] <= 0 || (bf != 0 && bf != 1)) return 0;
@@ -501,7 +508,7 @@ int stack_layout(const int* desc, StackBlock* blk, StackTotals& t, int min_tiles
     // (block 0 is sized for a caller that passes x16; without it the block stays on the per-block path and its region unused)
     for (int i = 0; i < n; ++i) {
         blk[i].defer_off = -1;
-        if (ir_wgrad_defer_ok(blk[i].s, i == 0 || blk[i - 1].y16 >= 0, min_tiles)) {
+        if (ir_wgrad_defer_ok(blk[i].s, i == 0 || blk[i - 1].y16 >= 0, WG_TIER_WIDE, min_tiles)) {
             blk[i].defer_off = (long long)t.bwd_ws;
             t.bwd_ws += ir_defer_bytes(blk[i].s);
         }
@@ -509,49 +516,46 @@ int stack_layout(const int* desc, StackBlock* blk, StackTotals& t, int min_tiles
     return 1;
 }
 
-// Where the backward walk (blocks n-1 .. 0) flushes the deferred gradients.  flush[i] = tiles flushed right after block i's
-// backward, > 0: one grouped launch, < 0: too few to fill the chip, the ordinary per-problem launches (0: no flush).  A flush
-// falls where the pending problems hold >= min_flush tiles and the next block would not fit into the same launch (it does not
-// defer, or would take the launch past one tile per CU or WG_GROUP_MAX problems), and where the walk leaves the stack.
-void stack_flush_plan(const StackBlock* blk, int n, bool have_x16, int min_flush, bool* defer, int* flush) {
+// What the backward walk (blocks n-1 .. 0) does with block i's two 1x1 weight gradients.  tier: whose launch they wait for (-1:
+// none, the block launches them itself); off: byte offset in the backward workspace of the region that keeps da3 / da1 until then
+// (-1: none).  flush / flush2: tiles of tier 1 / workgroups of tier 2 flushed right after block i's backward, > 0: one grouped
+// launch, < 0: too few to fill the chip, the ordinary per-problem launches (0: no flush).
+struct WgBlockPlan { int tier; long long off; int flush, flush2; };
+// Tier 1 (wide blocks, regions of their own: stack_layout): a flush falls where the pending problems hold >= min_flush_tiles tiles
+// and the next block would not fit into the same launch (it does not defer, or would take the launch past one tile per CU or
+// WG_GROUP_MAX problems), and where the walk leaves the stack.
+// Tier 2 (narrow blocks): once a tier-1 flush is enqueued, the flushed blocks' regions are dead, and a later block of the walk
+// whose gradients are problems of the 128 x 128 launch parks ITS da3 / da1 there (first fit, 256-aligned; same stream, so the
+// flush has read a region before the block writes it): no regions of its own, no new bytes.  A tier-2 flush falls where the next
+// block cannot join, at WG_GROUP_MAX problems, and where the walk ends; it returns what tier 2 borrowed.
+void stack_wgrad_plan(const StackBlock* blk, int n, bool have_x16, const WgThresholds& th, WgBlockPlan* plan) {
     int tiles = 0, count = 0;
     for (int i = n - 1; i >= 0; --i) {
-        defer[i] = blk[i].defer_off >= 0 && (i > 0 || have_x16);
-        flush[i] = 0;
-        if (defer[i]) { tiles += ir_wgrad_defer_tiles(blk[i].s); count += 2; }
+        const bool defer = blk[i].defer_off >= 0 && (i > 0 || have_x16);
+        plan[i] = WgBlockPlan{defer ? WG_TIER_WIDE : -1, defer ? blk[i].defer_off : -1, 0, 0};
+        if (defer) { tiles += ir_wgrad_defer_tiles(blk[i].s, WG_TIER_WIDE); count += 2; }
         if (!count) continue;
         const bool next = i > 0 && blk[i - 1].defer_off >= 0 && (i > 1 || have_x16);
-        const bool fits = next && count + 2 <= 16 && tiles + ir_wgrad_defer_tiles(blk[i - 1].s) <= 256;
-        if (i == 0 || count + 2 > 16 || (tiles >= min_flush && !fits)) {
-            flush[i] = tiles >= min_flush ? tiles : -tiles;
+        const bool fits = next && count + 2 <= WG_GROUP_MAX && tiles + ir_wgrad_defer_tiles(blk[i - 1].s, WG_TIER_WIDE) <= WG_GROUP_CHIP_TILES;
+        if (i == 0 || count + 2 > WG_GROUP_MAX || (tiles >= th.min_flush_tiles && !fits)) {
+            plan[i].flush = tiles >= th.min_flush_tiles ? tiles : -tiles;
             tiles = count = 0;
         }
     }
-}
-
-// Tier 2 (narrow blocks): once a tier-1 flush is enqueued, the flushed blocks' regions are dead, and a later block of the walk
-// whose gradients are problems of the 128 x 128 launch parks ITS da3 / da1 there (first fit, 256-aligned; same stream, so the
-// flush has read a region before the block writes it): no regions of its own, no new bytes.  off2[i]: byte offset of block i's
-// borrowed region (-1: it does not defer); flush2[i]: workgroups flushed right after block i's backward, > 0 in one small-tile
-// launch, < 0 (fewer than min_small) through the per-problem launches.  A tier-2 flush falls where the next block cannot join,
-// at WG_GROUP_MAX problems, and where the walk ends; it returns what tier 2 borrowed.  min_small 0: tier 2 off.
-int wg_min_flush_small = 96;
-void stack_flush_plan2(const StackBlock* blk, int n, bool have_x16, const bool* defer, const int* flush, int min_small, long long* off2,
-                       int* flush2) {
     struct Span { long long off; size_t bytes; };
     Span dead[32], avail[32];                              // regions of flushed tier-1 blocks; what is left of them
     int ndead = 0, wait1[32], nwait1 = 0;                  // tier-1 blocks not flushed yet
-    int wgs = 0, count = 0;
+    int wgs = 0;
+    count = 0;
     auto end2 = [&](int at) {
-        flush2[at] = wgs >= min_small ? wgs : -wgs;
+        plan[at].flush2 = wgs >= th.min_flush_small ? wgs : -wgs;
         wgs = count = 0;
         for (int j = 0; j < ndead; ++j) avail[j] = dead[j];
     };
     for (int i = n - 1; i >= 0; --i) {
-        off2[i] = -1;
-        flush2[i] = 0;
         const size_t need = ir_defer_bytes(blk[i].s);
-        const bool can = min_small > 0 && !defer[i] && ir_wgrad_defer_small_ok(blk[i].s, i > 0 ? blk[i - 1].y16 >= 0 : have_x16);
+        const bool can = th.min_flush_small > 0 && plan[i].tier < 0 &&
+                         ir_wgrad_defer_ok(blk[i].s, i > 0 ? blk[i - 1].y16 >= 0 : have_x16, WG_TIER_SMALL, 0);
         auto first_fit = [&]() {
             for (int j = 0; can && j < ndead; ++j)
                 if (avail[j].bytes >= need) return j;
@@ -563,18 +567,40 @@ void stack_flush_plan2(const StackBlock* blk, int n, bool have_x16, const bool* 
             slot = first_fit();                            // (the regions were full: a new list starts here)
         }
         if (slot >= 0) {
-            off2[i] = avail[slot].off;
+            plan[i].tier = WG_TIER_SMALL;
+            plan[i].off = avail[slot].off;
             avail[slot].off += (long long)need; avail[slot].bytes -= need;      // (ir_defer_bytes is a multiple of 256)
-            wgs += ir_wgrad_defer_small_tiles(blk[i].s);
+            wgs += ir_wgrad_defer_tiles(blk[i].s, WG_TIER_SMALL);
             count += 2;
-            if (i == 0 || count + 2 > 16) end2(i);
+            if (i == 0 || count + 2 > WG_GROUP_MAX) end2(i);
         }
-        if (defer[i]) wait1[nwait1++] = i;
-        if (flush[i]) {
+        if (plan[i].tier == WG_TIER_WIDE) wait1[nwait1++] = i;
+        if (plan[i].flush) {
             for (int j = 0; j < nwait1; ++j) dead[ndead] = avail[ndead] = Span{blk[wait1[j]].defer_off, ir_defer_bytes(blk[wait1[j]].s)}, ++ndead;
             nwait1 = 0;
         }
     }
+}
+
+// the body of v100_ir_stack_wgrad_plan (tier 1) and v100_ir_stack_wgrad_plan2 (tier 2): the plan's columns of one tier
+int stack_wgrad_plan_table(const int* desc, int have_x16, const WgThresholds& th, int tier, long long* out) {
+    if (!desc || !out) return V100_ERR_NULL;
+    if (th.min_problem_tiles < 1 || th.min_flush_tiles < 1 || th.min_flush_small < 0) return V100_ERR_SHAPE;
+    StackBlock blk[32];
+    StackTotals t;
+    if (!stack_layout(desc, blk, t, th.min_problem_tiles)) return V100_ERR_SHAPE;
+    const int n = desc[ST_N];
+    WgBlockPlan plan[32];
+    stack_wgrad_plan(blk, n, have_x16 != 0, th, plan);
+    size_t shared = t.bwd_ws;
+    for (int i = 0; i < n; ++i) {
+        out[3 * i] = plan[i].tier == tier;
+        out[3 * i + 1] = tier == WG_TIER_WIDE ? blk[i].defer_off : plan[i].tier == tier ? plan[i].off : -1;
+        out[3 * i + 2] = tier == WG_TIER_WIDE ? plan[i].flush : plan[i].flush2;
+        if (blk[i].defer_off >= 0 && (size_t)blk[i].defer_off < shared) shared = (size_t)blk[i].defer_off;
+    }
+    out[3 * n] = (long long)t.bwd_ws; out[3 * n + 1] = (long long)shared;
+    return V100_OK;
 }
 }   // namespace
 
@@ -582,59 +608,30 @@ void stack_flush_plan2(const StackBlock* blk, int n, bool have_x16, const bool* 
 // tests lower them to reach the grouped path at small shapes.  Changes v100_ir_stack_plan's bwd_ws_bytes: set before planning.
 extern "C" int v100_ir_stack_wgrad_group_thresholds(int min_problem_tiles, int min_flush_tiles) {
     if (min_problem_tiles < 1 || min_flush_tiles < 1) return V100_ERR_SHAPE;
-    wg_min_problem_tiles = min_problem_tiles;
-    wg_min_flush_tiles = min_flush_tiles;
+    wg_thresholds.min_problem_tiles = min_problem_tiles;
+    wg_thresholds.min_flush_tiles = min_flush_tiles;
     return V100_OK;
 }
 
-// The least workgroups of a tier-2 (small-tile) flush that go in one launch (stack_flush_plan2); 0 turns tier 2 off.
+// The least workgroups of a tier-2 (small-tile) flush that go in one launch (stack_wgrad_plan); 0 turns tier 2 off.
 extern "C" int v100_ir_stack_wgrad_group2_threshold(int min_flush_small) {
     if (min_flush_small < 0) return V100_ERR_SHAPE;
-    wg_min_flush_small = min_flush_small;
+    wg_thresholds.min_flush_small = min_flush_small;
     return V100_OK;
 }
 
 // Host only (no GPU call): what v100_ir_stack_bwd does with the weight gradients of this descriptor at these thresholds.
 // out (HOST long longs, 3 per block + 2): {defers, byte offset of the block's region in the backward workspace (-1: none),
-// flush (see stack_flush_plan)}; then {bwd_ws_bytes, bytes of the shared part in front of the regions}.
+// flush (see WgBlockPlan)}; then {bwd_ws_bytes, bytes of the shared part in front of the regions}.
 extern "C" int v100_ir_stack_wgrad_plan(const int* desc, int have_x16, int min_problem_tiles, int min_flush_tiles, long long* out) {
-    if (!desc || !out) return V100_ERR_NULL;
-    if (min_problem_tiles < 1 || min_flush_tiles < 1) return V100_ERR_SHAPE;
-    StackBlock blk[32];
-    StackTotals t;
-    if (!stack_layout(desc, blk, t, min_problem_tiles)) return V100_ERR_SHAPE;
-    const int n = desc[ST_N];
-    bool defer[32]; int flush[32];
-    stack_flush_plan(blk, n, have_x16 != 0, min_flush_tiles, defer, flush);
-    size_t shared = t.bwd_ws;
-    for (int i = 0; i < n; ++i) {
-        out[3 * i] = defer[i]; out[3 * i + 1] = blk[i].defer_off; out[3 * i + 2] = flush[i];
-        if (blk[i].defer_off >= 0 && (size_t)blk[i].defer_off < shared) shared = (size_t)blk[i].defer_off;
-    }
-    out[3 * n] = (long long)t.bwd_ws; out[3 * n + 1] = (long long)shared;
-    return V100_OK;
+    return stack_wgrad_plan_table(desc, have_x16, WgThresholds{min_problem_tiles, min_flush_tiles, 0}, WG_TIER_WIDE, out);
 }
 
 // As v100_ir_stack_wgrad_plan, for tier 2: out = 3 per block {defers to the small-tile launch, byte offset of the region it borrows
-// (-1: none), flush (stack_flush_plan2)}; then the same two totals (tier 2 adds no bytes).
+// (-1: none), flush2}; then the same two totals (tier 2 adds no bytes).
 extern "C" int v100_ir_stack_wgrad_plan2(const int* desc, int have_x16, int min_problem_tiles, int min_flush_tiles, int min_flush_small,
                                          long long* out) {
-    if (!desc || !out) return V100_ERR_NULL;
-    if (min_problem_tiles < 1 || min_flush_tiles < 1 || min_flush_small < 0) return V100_ERR_SHAPE;
-    StackBlock blk[32];
-    StackTotals t;
-    if (!stack_layout(desc, blk, t, min_problem_tiles)) return V100_ERR_SHAPE;
-    const int n = desc[ST_N];
-    bool defer[32]; int flush[32], flush2[32]; long long off2[32];
-    stack_flush_plan(blk, n, have_x16 != 0, min_flush_tiles, defer, flush);
-    stack_flush_plan2(blk, n, have_x16 != 0, defer, flush, min_flush_small, off2, flush2);
-    size_t shared = t.bwd_ws;
-    for (int i = 0; i < n; ++i) {
-        out[3 * i] = off2[i] >= 0; out[3 * i + 1] = off2[i]; out[3 * i + 2] = flush2[i];
-        if (blk[i].defer_off >= 0 && (size_t)blk[i].defer_off < shared) shared = (size_t)blk[i].defer_off;
-    }
-    out[3 * n] = (long long)t.bwd_ws; out[3 * n + 1] = (long long)shared;
-    return V100_OK;
+    return stack_wgrad_plan_table(desc, have_x16, WgThresholds{min_problem_tiles, min_flush_tiles, min_flush_small}, WG_TIER_SMALL, out);
 }
 
 extern "C" long long v100_ir_stack_plan(const int* desc, long long* plan) {
@@ -714,38 +711,34 @@ extern "C" int v100_ir_stack_bwd(const int* desc, const void* const* params, con
         return grad16_on && desc[ST_LEVEL] >= 5 && s.act16 >= 3 && s.S == 1 && s.T >= 8 && chan_bn3_bwd_fits(s.B, s.T) && ir_act16_supported(s) &&
                dw_bwd_da1_supported(s.B, s.hid, s.T, s.K, v100_dw_num_groups(s.B, s.hid));
     };
-    // Deferred weight gradients (stack_flush_plan): the wide blocks' 1x1 weight gradients wait for one grouped launch, one tile per
-    // CU through the whole contraction, instead of a split-K launch + slab reduction each.  Same sums in the same order.
-    bool defer[32]; int flush[32];
-    stack_flush_plan(blk, n, x16 != nullptr, wg_min_flush_tiles, defer, flush);
-    // Tier 2 (stack_flush_plan2): the narrow blocks' wait in the regions a tier-1 flush has left dead, for one small-tile launch.
-    long long off2[32]; int flush2[32];
-    stack_flush_plan2(blk, n, x16 != nullptr, defer, flush, wg_min_flush_small, off2, flush2);
-    // pending problems of the two tiers (v100_pw_wgrad_group's tables), their blocks
-    struct Pending { const void* gp[5 * 16]; int gd[8 * 16]; int gblk[16]; int ng; } pend[2];
-    pend[0].ng = pend[1].ng = 0;
-    auto flush_pending = [&](int tier, bool grouped) -> int {
+    // Deferred weight gradients (stack_wgrad_plan): the wide blocks' 1x1 weight gradients wait for one grouped launch, one tile per
+    // CU through the whole contraction, instead of a split-K launch + slab reduction each.  Same sums in the same order.  Tier 2:
+    // the narrow blocks' wait in the regions a tier-1 flush has left dead, for one small-tile launch.
+    WgBlockPlan plan[32];
+    stack_wgrad_plan(blk, n, x16 != nullptr, wg_thresholds, plan);
+    // pending problems of the two tiers, their blocks
+    struct Pending { WgGroupProblem pr[WG_GROUP_MAX]; int blk[WG_GROUP_MAX]; int n; } pend[2];
+    pend[0].n = pend[1].n = 0;
+    auto flush_pending = [&](WgTier tier, bool grouped) -> int {
         Pending& q = pend[tier];
-        const void* const* gp = q.gp; const int* gd = q.gd; const int* gblk = q.gblk; int& ng = q.ng;
         int rc = V100_OK;
-        if (grouped) rc = tier ? v100_pw_wgrad_group_small(ng, gp, gd, stream) : v100_pw_wgrad_group(ng, gp, gd, stream);
+        if (grouped) rc = pw_wgrad_group_launch(tier, q.n, q.pr, (hipStream_t)stream);
         else
-            for (int j = 0; j < ng && rc == V100_OK; ++j) {                 // too few tiles: split-K per problem, slabs in the shared workspace
+            for (int j = 0; j < q.n && rc == V100_OK; ++j) {               // too few tiles: split-K per problem, slabs in the shared workspace
                 IrBwdWs w;
-                ir_bwd_carve(blk[gblk[j]].s, w0, w);
-                const int* d = gd + 8 * j;
-                rc = v100_pw_wgrad_io(gp[5 * j], nullptr, nullptr, nullptr, nullptr, d[5], gp[5 * j + 1], (const float*)gp[5 * j + 2],
-                                      (const float*)gp[5 * j + 3], d[6], w.slab, (float*)const_cast<void*>(gp[5 * j + 4]), d[4], d[0], d[1], d[2], d[3],
-                                      d[7], stream);
+                ir_bwd_carve(blk[q.blk[j]].s, w0, w);
+                const WgGroupProblem& p = q.pr[j];
+                rc = v100_pw_wgrad_io(p.G, nullptr, nullptr, nullptr, nullptr, 0, p.X, p.xa, p.xb, p.x_mode, w.slab, p.dW, p.S, p.B, p.M, p.K, p.T,
+                                      WG_IO_G | WG_IO_X, stream);
             }
-        ng = 0;
+        q.n = 0;
         return rc;
     };
     bool dy_is16 = false;
     for (int i = n - 1; i >= 0; --i) {
         const StackBlock& b = blk[i];
         IrShape s = b.s;
-        const int tier = defer[i] ? 0 : off2[i] >= 0 ? 1 : -1;      // whose launch the block's two 1x1 weight gradients wait for
+        const int tier = plan[i].tier;                           // whose launch the block's two 1x1 weight gradients wait for
         s.defer = tier >= 0;
         // dx of block i is dy of block i - 1: 16-bit when both are capable blocks (with or without a residual)
         const bool dx_is16 = i > 0 && grad16_ok(i) && grad16_ok(i - 1);
@@ -756,25 +749,17 @@ extern "C" int v100_ir_stack_bwd(const int* desc, const void* const* params, con
         const IrParams p = ir_params(params + 18 * i);
         const void* x16i = i > 0 ? (blk[i - 1].y16 >= 0 ? (const void*)(base + blk[i - 1].y16) : nullptr) : x16;
         IrBwdArgs a{i > 0 ? at(blk[i - 1].y) : (const float*)x, at(b.a1), at(b.a2), at(b.a3), p.w1, p.wd, p.w3, p.bn1.gamma, p.bn2.gamma, p.bn3.gamma,
-                    at(b.coef), (const float*)dyi, (float*)dxi, {}, w0, (void*)(base + b.prep), x16i, tier >= 0 ? w0 + (tier ? off2[i] : b.defer_off) : nullptr};
+                    at(b.coef), (const float*)dyi, (float*)dxi, {}, w0, (void*)(base + b.prep), x16i, tier >= 0 ? w0 + plan[i].off : nullptr};
         ir_grads_carve(s, (float*)grads + goff, a.g);
         CK(ir_bwd(s, a, (hipStream_t)stream));
         if (tier >= 0) {
-            const IrBnCoef bn2 = ir_coef(a.coef, s.mc).bn2;
-            char* own = (char*)a.defer_region;
             Pending& q = pend[tier];
-            // project gradient: dW3 = da3 x relu6(s2 a2 + t2); expand gradient: dW1 = da1 x (shadow of the block input)
-            const void* pr[2][5] = {{own, a.a2, bn2.s, bn2.t, a.g.dW3}, {own + ir_defer_da3_bytes(s), a.x16, nullptr, nullptr, a.g.dW1}};
-            const int dm[2][8] = {{s.B, s.cout, s.hid, s.T, v100_pw_wgrad_splits(s.B, s.cout, s.hid), 0, 1, WG_IO_G | WG_IO_X},
-                                  {s.B, s.hid, s.cin, s.T, v100_pw_wgrad_splits(s.B, s.hid, s.cin), 0, 0, WG_IO_G | WG_IO_X}};
-            for (int j = 0; j < 2; ++j, ++q.ng) {
-                for (int e = 0; e < 5; ++e) q.gp[5 * q.ng + e] = pr[j][e];
-                for (int e = 0; e < 8; ++e) q.gd[8 * q.ng + e] = dm[j][e];
-                q.gblk[q.ng] = i;
-            }
+            ir_wgrad_problems(s, &a, q.pr + q.n);
+            q.blk[q.n] = q.blk[q.n + 1] = i;
+            q.n += 2;
         }
-        if (flush[i]) CK(flush_pending(0, flush[i] > 0));
-        if (flush2[i]) CK(flush_pending(1, flush2[i] > 0));
+        if (plan[i].flush) CK(flush_pending(WG_TIER_WIDE, plan[i].flush > 0));
+        if (plan[i].flush2) CK(flush_pending(WG_TIER_SMALL, plan[i].flush2 > 0));
         dyi = dxi;
         dy_is16 = dx_is16;
     }

@@ -2,16 +2,9 @@
 // its tile through the whole contraction (no split-K slabs, no reduce launch).
 #pragma once
 #include "pointwise_bf16_wgrad_ws.h"
+#include "wgrad_group.h"
 
-// One problem of a grouped launch: dW[M][K] = sum_{b,t} G[b][m][t] * x'[b][k][t], both operands bf16-stored (WG_IO_G | WG_IO_X),
-// G plain, X plain (x_mode 0: the expand gradient on da1, 128 x 256 tile) or relu6(xa x + xb) (x_mode 1: the project gradient,
-// 256 x 128 tile).  S: the split count whose summation order the workgroup reproduces (v100_pw_wgrad_splits).
-struct WgGroupProblem {
-    const void* G; const void* X; const float* xa; const float* xb; float* dW;
-    int B, M, K, T, S, x_mode;
-    int xcd, slot0, ntiles;      // placement (launcher): tile i of the problem runs as workgroup 8 * (slot0 + i) + xcd
-};
-#define WG_GROUP_MAX 16
+// The problem record, WG_GROUP_MAX and the tiers: wgrad_group.h.  Here x_mode 1 runs on a 256 x 128 tile, x_mode 0 on 128 x 256.
 #define WG_GROUP_RL 2
 struct WgGroupParams { WgGroupProblem pr[WG_GROUP_MAX]; int n; };
 

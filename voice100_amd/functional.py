@@ -17,7 +17,7 @@ import ctypes
 import functools
 import weakref
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -381,8 +381,17 @@ def set_wgrad_group2_threshold(min_flush_small: int = 96) -> None:
     N.call("v100_ir_stack_wgrad_group2_threshold", int(min_flush_small))
 
 
+class StackBlockPlan(NamedTuple):
+    """v100_ir_stack_plan's eight numbers of a block: byte offsets into the blob (y16 -1: no shadow) and the output length."""
+    a1: int; a2: int; a3: int; y: int; y16: int; coef: int; prep: int; t_out: int
+
+
+class StackTotals(NamedTuple):
+    blob_bytes: int; bwd_ws_bytes: int; grad_floats: int; fwd_ws_offset: int
+
+
 def _stack_plan(cfgs, B, T, bf16, level, last_shadow):
-    """(desc ctypes array, per-block offsets, totals) of a run of blocks at this input shape: computed once per distinct key."""
+    """(desc ctypes array, a StackBlockPlan per block, StackTotals) of a run of blocks at this input shape: computed once per distinct key."""
     key = (cfgs, B, T, bf16, level, last_shadow)
     ent = _STACK_PLANS.get(key)
     if ent is None:
@@ -393,7 +402,7 @@ def _stack_plan(cfgs, B, T, bf16, level, last_shadow):
             raise RuntimeError("InvertedResidual stack: invalid shape")
         if len(_STACK_PLANS) > 256:                 # time-stretched lengths: at most ~100 distinct T per run
             _STACK_PLANS.clear()
-        ent = _STACK_PLANS[key] = (desc, [tuple(plan[8 * i:8 * i + 8]) for i in range(n)], tuple(plan[8 * n:8 * n + 6]))
+        ent = _STACK_PLANS[key] = (desc, [StackBlockPlan(*plan[8 * i:8 * i + 8]) for i in range(n)], StackTotals(*plan[8 * n:8 * n + 4]))
     return ent
 
 
@@ -419,17 +428,17 @@ class IRStackTrainFn(torch.autograd.Function):
         desc, blocks, totals = _stack_plan(cfgs, B, T, bf16, level, bool(last_shadow))
         if not (bf16 == 1 and level >= 4):
             x16 = None
-        blob = torch.empty(totals[0], dtype=torch.uint8, device=x.device)
+        blob = torch.empty(totals.blob_bytes, dtype=torch.uint8, device=x.device)
         ptab = (ctypes.c_void_p * (18 * n))(*[t.data_ptr() for t in params])
         N.call("v100_ir_stack_fwd_train", desc, ptab, x, x16, blob)
         _touched([params[18 * i + j] for i in range(n) for j in _STAT_SLOTS])     # the blocks' running statistics
         o = blocks[-1]
-        cout, T2 = cfgs[-1][2], o[7]
-        y = blob[o[3]:o[3] + 4 * B * cout * T2].view(torch.float32).view(B, cout, T2)
+        cout, T2 = cfgs[-1][2], o.t_out
+        y = blob[o.y:o.y + 4 * B * cout * T2].view(torch.float32).view(B, cout, T2)
         y16 = None
-        if o[4] >= 0:
+        if o.y16 >= 0:
             P2 = pitch16(T2, B)
-            y16 = blob[o[4]:o[4] + 2 * B * cout * P2].view(torch.bfloat16).view(B, cout, P2)
+            y16 = blob[o.y16:o.y16 + 2 * B * cout * P2].view(torch.bfloat16).view(B, cout, P2)
             ctx.mark_non_differentiable(y16)
         ctx.set_materialize_grads(False)
         # (plain attributes, not save_for_backward: y is a view of the blob, and the fused optimiser updates parameters through raw
@@ -451,10 +460,10 @@ class IRStackTrainFn(torch.autograd.Function):
         dy = dy.contiguous()
         # under data parallelism the gradients are written straight into the exchange buffer (no packing copy): same values, another home
         weights = [params[18 * b + j] for b in range(n) for j in _TRAINABLE_SLOTS]
-        grads = _grad_arena_for(weights, totals[2]) if _GRAD_ARENAS else None
+        grads = _grad_arena_for(weights, totals.grad_floats) if _GRAD_ARENAS else None
         if grads is None:
-            grads = _f32(totals[2], like=x)
-        ws = torch.empty(totals[1], dtype=torch.uint8, device=x.device)
+            grads = _f32(totals.grad_floats, like=x)
+        ws = torch.empty(totals.bwd_ws_bytes, dtype=torch.uint8, device=x.device)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         N.call("v100_ir_stack_bwd", ctx.desc, ctx.ptab, x, ctx.x16, ctx.blob, dy, dx, grads, ws)
         ctx.blob = None                                   # the activations are dead: free them before the rest of backward runs
