@@ -690,6 +690,27 @@ int v100_ctc_segment(const float* logits, const int* in_len, const long long* la
                      int* start, int* end, float* duration, float* log_conf, int* word_first, int* word_count, int* word_start,
                      int* word_end, float* word_log_conf, int* n_words, int B, int T, int V, int Lmax, int blank, long long sep,
                      void* stream);
+/* K33, the same for chapter-length recordings (csrc/ctc_segment_long.hip): K26's forward-backward restricted to a corridor.  Frames
+ * come in blocks of v100_ctc_segment_long_block() = 16; lo [B][ceil(T/16)] int32 is the first live state of each block and band = W the
+ * number of live states: state s of the n = 2 L + 1 is live at frame t iff lo[t >> 4] <= s < lo[t >> 4] + W.  alpha, beta and the
+ * enter / leave terms are zero at every dead state and everything else follows, so every output is the posterior over the
+ * alignments that stay inside the corridor; lo = 0 with band >= n is K26's quantity.  tests/_ctc_segment_long_ref.py defines it in
+ * float64.  Memory safety does not rest on lo: the device clamps each value to [0, hi], hi = (max(n - W, 0) + 1) & ~1, clears bit 0
+ * and takes the running maximum.  Inputs and outputs are K26's, with log_prob [B] in fp64 and ok [B] int32 = 1 where p > 0; a row
+ * with p = 0 (the corridor misses the end, too few frames, a label equal to blank or outside [0, V)) gets ok 0 and K26's infeasible
+ * outputs, its words still delimited; T_b = 0 gives ok 1 and log_prob 0 iff the row has no label.  Exponents are integers relative
+ * to their block, with one int64 offset per block, so 2^20 frames of any logits stay exact; an emission below 2^-(2^22) counts as 0.
+ * Two launches (the second sums the words); no float atomics: two calls give equal bits.
+ * ws: v100_ctc_segment_long_workspace_bytes(B, T, Lmax, band) bytes = 12 B T band / 2 for alpha and the entering share per frame and
+ * live label, plus 12 bytes per block and 4 per label, each part rounded up to 16 (a host helper; 0 = unsupported shape).
+ * B >= 1, 1 <= T <= 2^20, 0 <= Lmax <= 2^19, 2 <= V <= 128, 0 <= blank < V, band a multiple of 64 in [64, 1024], else 1; a NULL
+ * required pointer (in_len and lab_len excepted), or some but not all of the word pointers, 3; both before anything touches a device. */
+long long v100_ctc_segment_long_workspace_bytes(int B, int T, int Lmax, int band);
+int v100_ctc_segment_long_block(void);
+int v100_ctc_segment_long(const float* logits, const int* in_len, const long long* labels, const int* lab_len, const int* lo, void* ws,
+                          double* log_prob, int* ok, int* start, int* end, float* duration, float* log_conf, int* word_first,
+                          int* word_count, int* word_start, int* word_end, float* word_log_conf, int* n_words, int B, int T, int V,
+                          int Lmax, int band, int blank, long long sep, void* stream);
 /* K27, objective scores of synthesised WORLD features (csrc/dtw.hip): dynamic time warping between x [B][Tx][D] fp32 (the hypothesis)
  * and y [B][Ty][D] fp32 (the reference), rows of x_len / y_len [B] int32 frames (NULL = full width; clamped to [0, width] on the
  * device; nothing beyond a row's length is read), and the sums along the warping path.  With n, m the two lengths of a pair:

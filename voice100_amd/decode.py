@@ -10,7 +10,8 @@ forward-backward over the alignments of a given transcript, reduced to time boun
 nor ctc_align_long (K29): the banded Viterbi that aligns a chapter-length recording to its text, nor ctc_cut_points (K31): where to
 cut a recording of any length, at its pauses, into pieces that the beam search and ctc_segment take, nor CTCBeamStream and
 ctc_beam_search_long (K32): the beam search kept between calls, so that logits can be pushed chunk by chunk and a recording of any
-length is decoded as one utterance, bit for bit what one call over all its frames would give."""
+length is decoded as one utterance, bit for bit what one call over all its frames would give, nor ctc_segment_long and
+ctc_corridor (K33): ctc_segment inside a corridor round a path, for recordings of up to 2^20 frames."""
 import math
 from typing import NamedTuple, Optional
 
@@ -517,7 +518,8 @@ def ctc_segment(logits: torch.Tensor, lengths: torch.Tensor, labels: torch.Tenso
     start < end <= the next label's start.  A word is a maximal run of labels != sep (edit_distance's rule); sep=None: no word level.
     Lengths are clamped to [0, T] / [0, L] on the device and nothing beyond them is read; outputs beyond them are 0.  A row whose
     labels cannot be aligned (too few frames, a label equal to blank or outside [0, V)) gets log_prob -inf, start = end = 0,
-    duration 0 and log_confidence -inf.  Two calls give equal bits.  Limits: 1 <= T <= 4096, 2 <= V <= 128, L <= 2047."""
+    duration 0 and log_confidence -inf.  Two calls give equal bits.  Limits: 1 <= T <= 4096, 2 <= V <= 128, L <= 2047; beyond them
+    ctc_segment_long computes the same inside a corridor round a path."""
     given = [t for t in (logits, lengths, labels, label_lengths) if t is not None]
     if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in given) or logits is None or labels is None:
         raise RuntimeError("ctc_segment: GPU tensors only")
@@ -553,3 +555,136 @@ def ctc_segment(logits: torch.Tensor, lengths: torch.Tensor, labels: torch.Tenso
         start, end, duration, log_conf = (t[:, :0] for t in (start, end, duration, log_conf))
         word = tuple(t[:, :0] for t in word[:5]) + (word[5],) if sep is not None else word
     return CTCSegments(log_prob, start, end, duration, log_conf, *word)
+
+
+class CTCLongSegments(NamedTuple):
+    """What ctc_segment_long returns: CTCSegments' fields, log_prob in fp64, and ok; the word fields are None with sep=None."""
+    log_prob: torch.Tensor                               # [B] fp64: log p(labels | logits) over the alignments inside the corridor
+    ok: torch.Tensor                                     # [B] int32: 1 where that probability is not zero
+    start: torch.Tensor                                  # [B, L] int32
+    end: torch.Tensor                                    # [B, L] int32
+    duration: torch.Tensor                               # [B, L] fp32
+    log_confidence: torch.Tensor                         # [B, L] fp32
+    word_first: Optional[torch.Tensor]                   # [B, (L + 1) // 2] int32
+    word_count: Optional[torch.Tensor]
+    word_start: Optional[torch.Tensor]
+    word_end: Optional[torch.Tensor]
+    word_log_confidence: Optional[torch.Tensor]
+    n_words: Optional[torch.Tensor]                      # [B] int32
+
+
+def ctc_corridor(path: torch.Tensor, lengths, label_lengths, band: int = 256) -> torch.Tensor:
+    """The corridor that ctc_segment_long walks, from a CTC path: path [B, T] int32 (extended positions, as ctc_align_long returns
+    them), lengths [B] or None, label_lengths [B] (or one int for every row) -> lo [B, ceil(T / 16)] int32, the first live state of
+    every block of 16 frames.  With c_k = path[16 k], hi = (max(2 L + 1 - band, 0) + 1) & ~1:
+    lo_k = clamp((c_k + 16 - band / 2) & ~1, 0, hi), then a running maximum over k; blocks beyond a row's length repeat its last value.
+    A CTC path advances by at most 2 states a frame, so it stays inside [lo_k, lo_k + band) at any band >= 64.  Stock torch ops, no
+    read-back."""
+    if not isinstance(path, torch.Tensor) or path.dim() != 2 or path.shape[1] < 1:
+        raise RuntimeError("ctc_corridor: path must be a tensor [B, T] with T >= 1")
+    W = int(band)
+    if W < 64 or W > 1024 or W % 64:
+        raise RuntimeError(f"ctc_corridor: band = {W} must be a multiple of 64 in [64, 1024]")
+    B, T = path.shape
+    dev = path.device
+    NB = (T + 15) // 16
+    idx = (torch.arange(NB, device=dev) * 16)[None].expand(B, NB)
+    if lengths is not None:
+        last = (lengths.to(device=dev, dtype=torch.int64).reshape(B).clamp(0, T) - 1).clamp_min(0)
+        idx = torch.minimum(idx, (last // 16 * 16)[:, None])
+    ll = torch.as_tensor(label_lengths, device=dev).to(torch.int64).reshape(-1).expand(B)
+    hi = torch.bitwise_and((2 * ll + 1 - W).clamp_min(0) + 1, -2)
+    c = path.gather(1, idx).to(torch.int64)
+    lo = torch.minimum(torch.bitwise_and(c + (16 - W // 2), -2).clamp_min(0), hi[:, None])
+    return torch.cummax(lo, dim=1).values.to(torch.int32).contiguous()
+
+
+def ctc_segment_long(logits: torch.Tensor, lengths: torch.Tensor, labels: torch.Tensor, label_lengths: torch.Tensor, path=None, lo=None,
+                     band: int = 256, blank: int = 0, sep=1, align_band: int = 2048, path_ok=None) -> CTCLongSegments:
+    """ctc_segment for chapter-length recordings (K33, csrc/ctc_segment_long.hip): the same time boundaries, expected durations and
+    confidences of every label and word of a GIVEN transcript, from the CTC forward-backward over the alignments that stay inside a
+    CORRIDOR of `band` states around a path.  logits [B, T, V] fp32 (the model's output; the kernel normalises), lengths [B] or None,
+    labels [B, L] int64, label_lengths [B] or None -> CTCLongSegments of device tensors.  No read-back inside the call.
+
+    The corridor: frames come in blocks of 16, lo[b, k] is the first live state of block k (of the 2 L + 1 states: label i is state
+    2 i + 1), and a state is live where lo <= s < lo + band.  Alignments that leave the corridor count for nothing: every output is
+    the posterior over those that stay inside, and log_prob is at most ctc_segment's.  Where the frames pin the path down (a trained
+    model on its own transcript) nothing measurable is lost at band 64 already; on diffuse logits mass is cut -- widen band.
+    lo=: a corridor of the caller's, [B, ceil(T / 16)] int32; the device clamps it to [0, hi], clears bit 0 and takes the running
+    maximum before it trusts it.  path=: a CTC path [B, T] int32 (ctc_align_long's), from which ctc_corridor builds lo; with it
+    path_ok=: [B], the aligner's ok -- a row where it is 0 has a path of zeros, and comes back with ok = 0 and the outputs of a row
+    without an alignment, whatever the corridor of zeros would give.  Neither:
+    ctc_align_long runs on the log_softmax of the same logits at band `align_band`; a row that the aligner lost comes back with ok = 0.
+    lo = 0 everywhere with band >= 2 L + 1 is ctc_segment's quantity exactly.
+    A row whose corridor holds no alignment (it misses the end, too few frames, a label equal to blank or outside [0, V)) gets ok = 0,
+    log_prob -inf, start = end = 0, duration 0 and log_confidence -inf; its words are still delimited.  Lengths are clamped on the
+    device, nothing beyond them is read, outputs beyond them are 0.  Two calls give equal bits.  Memory: 12 T band / 2 bytes a row
+    (138 MB for 30 minutes at band 256).  Limits: 1 <= T <= 2^20, L <= 2^19, 2 <= V <= 128, band a multiple of 64 in [64, 1024]."""
+    given = [t for t in (logits, lengths, labels, label_lengths, path, lo, path_ok) if t is not None]
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in given) or logits is None or labels is None:
+        raise RuntimeError("ctc_segment_long: GPU tensors only")
+    if logits.dim() != 3 or labels.dim() != 2 or labels.shape[0] != logits.shape[0]:
+        raise RuntimeError(f"ctc_segment_long: logits [B, T, V] and labels [B, L] with the same B, got {list(logits.shape)} and "
+                           f"{list(labels.shape)}")
+    if path is not None and lo is not None:
+        raise RuntimeError("ctc_segment_long: give a path or a corridor, not both")
+    if path_ok is not None and (path is None or path_ok.numel() != logits.shape[0]):
+        raise RuntimeError(f"ctc_segment_long: path_ok goes with path= and has {logits.shape[0]} elements")
+    dev = logits.device
+    logits = logits.contiguous().float()
+    B, T, V = logits.shape
+    blank, band = int(blank), int(band)
+    labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+    il = lengths.to(device=dev, dtype=torch.int32).contiguous() if lengths is not None else None
+    ll = label_lengths.to(device=dev, dtype=torch.int32).contiguous() if label_lengths is not None else None
+    if (il is not None and il.numel() != B) or (ll is not None and ll.numel() != B):
+        raise RuntimeError(f"ctc_segment_long: lengths and label_lengths must have {B} elements")
+    width = labels.shape[1]
+    if width == 0:                                       # no column: every row is empty
+        labels, ll = labels.new_zeros((B, 1)), torch.zeros((B,), dtype=torch.int32, device=dev)
+    Lmax = labels.shape[1]
+    nbytes = N.helper("v100_ctc_segment_long_workspace_bytes", B, T, Lmax, band) if B >= 1 else 0
+    if nbytes <= 0 or not 2 <= V <= 128 or not 0 <= blank < V:
+        raise RuntimeError(f"ctc_segment_long: unsupported shape or argument (B = {B} >= 1, 1 <= T = {T} <= 2^20, 2 <= V = {V} <= 128, "
+                           f"L = {width} <= 2^19, 0 <= blank = {blank} < V and band = {band}, a multiple of 64 in [64, 1024], are the "
+                           "limits)")
+    NB = (T + 15) // 16
+    lost = path_ok.reshape(B) == 0 if path_ok is not None else None
+    if lo is None:
+        lens_l = ll.clamp(0, Lmax) if ll is not None else Lmax
+        if path is None:
+            al = ctc_align_long(torch.log_softmax(logits, dim=-1), labels, il, ll, band=align_band, blank=blank)
+            path, lost = al.path, al.ok == 0
+        if path.shape != (B, T):
+            raise RuntimeError(f"ctc_segment_long: path must be [{B}, {T}], got {list(path.shape)}")
+        lo = ctc_corridor(path.to(torch.int32), il, lens_l, band)
+    if lo.shape != (B, NB):
+        raise RuntimeError(f"ctc_segment_long: lo must be [{B}, {NB}] (one value per block of 16 frames), got {list(lo.shape)}")
+    lo = lo.to(torch.int32).contiguous()
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)    # noqa: E731
+    log_prob, ok = torch.empty((B,), dtype=torch.float64, device=dev), i32(B)
+    start, end, duration, log_conf = i32(B, Lmax), i32(B, Lmax), f32(B, Lmax), f32(B, Lmax)
+    NW = (Lmax + 1) // 2
+    word = (i32(B, NW), i32(B, NW), i32(B, NW), i32(B, NW), f32(B, NW), i32(B)) if sep is not None else (None,) * 6
+    N.call("v100_ctc_segment_long", logits, il, labels, ll, lo, ws, log_prob, ok, start, end, duration, log_conf, *word, B, T, V, Lmax,
+           band, blank, 0 if sep is None else int(sep))
+    if lost is not None:                                 # the aligner's lost rows: the infeasible outputs, whatever the corridor of zeros gave
+        row = lost[:, None]
+        inside = torch.arange(Lmax, device=dev)[None] < (ll[:, None] if ll is not None else Lmax)
+        ninf = torch.full((), float("-inf"), dtype=torch.float32, device=dev)
+        log_prob = torch.where(lost, ninf.double(), log_prob)
+        ok = torch.where(lost, torch.zeros_like(ok), ok)
+        start, end = torch.where(row, torch.zeros_like(start), start), torch.where(row, torch.zeros_like(end), end)
+        duration = torch.where(row, torch.zeros_like(duration), duration)
+        log_conf = torch.where(row & inside, ninf, log_conf)
+        if sep is not None:
+            wf, wc, wst, wen, wlc, nw = word
+            inw = torch.arange(NW, device=dev)[None] < nw[:, None]
+            word = (wf, wc, torch.where(row, torch.zeros_like(wst), wst), torch.where(row, torch.zeros_like(wen), wen),
+                    torch.where(row & inw, ninf, wlc), nw)
+    if width == 0:
+        start, end, duration, log_conf = (t[:, :0] for t in (start, end, duration, log_conf))
+        word = tuple(t[:, :0] for t in word[:5]) + (word[5],) if sep is not None else word
+    return CTCLongSegments(log_prob, ok, start, end, duration, log_conf, *word)

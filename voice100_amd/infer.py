@@ -745,18 +745,19 @@ class LongASRPipeline:
           -> decode.ctc_segment (timed, or greedy)         times and confidences of the labels and words of each segment     (K26)
           -> offsets                                       every frame index moves by its segment's start
 
-    The beam search and ctc_segment stop at 4096 frames and run one workgroup per row, so a recording is decoded as a batch of its
-    pieces.  Cutting inside a run of blank frames costs the greedy decode nothing (CTC never merges labels across a blank: the
-    pieces' decodes, concatenated, are the recording's); the beam search loses only what it would have carried across the pause,
+    The one-call beam search and ctc_segment stop at 4096 frames and run one workgroup per row, so a recording is decoded as a batch
+    of its pieces (their long forms, K32's ctc_beam_search_long and K33's ctc_segment_long, serve whole()).  Cutting inside a run of
+    blank frames costs the greedy decode nothing (CTC never merges labels across a blank: the pieces' decodes, concatenated, are the
+    recording's); the beam search loses only what it would have carried across the pause,
     and THE LANGUAGE MODEL'S CONTEXT RESTARTS AT EVERY CUT: each segment is scored as a sentence of its own.  A forced cut (a
     stretch of max_frames frames without an admissible pause) may split a word; its segment says so in "forced".  whole() (K32) has
     none of the three: it decodes the recording as one utterance with a resumable beam, one frame after the other, at many times
-    the cost and without confidences.
+    the cost; with confidences=True decode.ctc_segment_long (K33) adds the soft times and the confidences of its labels and words.
     An ASRPipeline is held and called for the decode; blank must be 0, as there.  Eval mode only, like windowed_logits.
     Device-to-host copies: the number of segments S, one copy of the calls' widths, and the longest hypothesis of each call."""
 
     def __init__(self, model, mel=None, beam_size=None, lm=None, lm_weight=0.5, length_bonus=0.0, keep=1500, max_frames=3000, min_gap=25,
-                 margin=0.0, pad=5, min_frames=50, max_batch=32, blank=0, sep=1, frame_seconds=None, band=2048):
+                 margin=0.0, pad=5, min_frames=50, max_batch=32, blank=0, sep=1, frame_seconds=None, band=2048, seg_band=256):
         if int(blank) != 0:
             raise RuntimeError(f"LongASRPipeline: blank = {blank}; the decode of ASRPipeline takes the blank at id 0")
         if int(max_batch) < 1:
@@ -766,6 +767,7 @@ class LongASRPipeline:
         self.model, self.mel = model, mel
         self.keep, self.max_batch, self.blank, self.sep = int(keep), int(max_batch), int(blank), sep
         self.band = int(band)                                # whole(): ctc_align_long's band
+        self.seg_band = int(seg_band)                        # whole(confidences=True): ctc_segment_long's band
         self.cut = dict(max_frames=int(max_frames), min_gap=min_gap, margin=float(margin), pad=int(pad), min_frames=int(min_frames))
 
     def _wave(self, path_or_wave, who):
@@ -895,7 +897,8 @@ class LongASRPipeline:
         return {"text": decode(torch.tensor(whole, dtype=torch.int64)), "utterances": utts, "frame_seconds": fs}
 
     @torch.no_grad()
-    def whole(self, path_or_wave=None, feats: torch.Tensor = None, logits: torch.Tensor = None, timed: bool = True, chunk: int = 4096):
+    def whole(self, path_or_wave=None, feats: torch.Tensor = None, logits: torch.Tensor = None, timed: bool = True, chunk: int = 4096,
+              confidences: bool = False):
         """The recording decoded as ONE utterance (K32): windowed_logits, then decode.ctc_beam_search_long over all its frames -- the
         beam is never restarted, the language model keeps one context, no cut can split a word -- and with timed=True
         decode.ctc_align_long of the best transcript on the log-softmax of the same logits (band = the constructor's).  The inputs
@@ -904,9 +907,15 @@ class LongASRPipeline:
         memory grows with the recording.  Returns a dict of device tensors: "ids" [L] int64 and "ids_len", "score" (0-dim; the fused
         score with a language model, then also "ctc_score" and "lm_score"); with timed "start", "end" [L] int32 = each label's first
         frame and one past its last on the best path (the cumulative sum of the aligner's frames per position) and "ok" (0-dim
-        int32; 0: the band lost the path, start = end = 0 -- widen band); and "frame_seconds".  There are NO confidences:
-        ctc_segment, which computes them, stops at 4096 frames.  One read-back, of ids_len, sizes L."""
-        from .decode import ctc_align_long, ctc_beam_search_long
+        int32; 0: the band lost the path, start = end = 0 -- widen band); and "frame_seconds".  confidences=True (it needs timed) adds
+        what decode.ctc_segment_long (K33) computes inside the corridor of seg_band states (the constructor's) round that path -- ctc_segment
+        itself stops at 4096 frames: "log_prob" (0-dim fp64), "soft_start", "soft_end" [L] int32 (the posterior medians, where
+        "start" / "end" are the best path's), "duration", "log_confidence" [L] fp32, the word fields "word_first", "word_count",
+        "word_start", "word_end", "word_log_confidence" and "n_words" (None without a separator id), and "seg_ok" (0-dim int32; 0:
+        no alignment inside the corridor, or the aligner lost the path: then the new keys hold what a row without an alignment gets,
+        log_prob -inf, times and durations 0, confidences -inf).  The other keys are what they are without it, bit for bit.
+        One read-back, of ids_len, sizes L."""
+        from .decode import ctc_align_long, ctc_beam_search_long, ctc_segment_long
         a = self.asr
         if a.beam_size is None:
             raise RuntimeError("LongASRPipeline.whole: the pipeline decodes greedily, and the greedy decodes of segments()' pieces "
@@ -931,17 +940,29 @@ class LongASRPipeline:
             al = ctc_align_long(torch.log_softmax(logits, dim=-1)[None], ids[None], None, n.reshape(1), band=self.band, blank=self.blank)
             ends = torch.cumsum(al.align[0], 0, dtype=torch.int32)[1:2 * L:2]        # label i sits at extended position 2 i + 1
             out.update({"start": ends - al.align[0, 1:2 * L:2], "end": ends, "ok": al.ok[0]})
+            if confidences:
+                seg = ctc_segment_long(logits[None], None, ids[None], n.reshape(1), path=al.path, path_ok=al.ok, band=self.seg_band,
+                                       blank=self.blank, sep=self.sep)
+                first = lambda t: None if t is None else t[0]                    # noqa: E731
+                out.update({"log_prob": seg.log_prob[0], "soft_start": seg.start[0], "soft_end": seg.end[0], "duration": seg.duration[0],
+                            "log_confidence": seg.log_confidence[0], "word_first": first(seg.word_first),
+                            "word_count": first(seg.word_count), "word_start": first(seg.word_start), "word_end": first(seg.word_end),
+                            "word_log_confidence": first(seg.word_log_confidence), "n_words": first(seg.n_words),
+                            "seg_ok": seg.ok[0]})
+        elif confidences:
+            raise RuntimeError("LongASRPipeline.whole: confidences=True needs timed=True (the corridor is built round the aligner's path)")
         out["frame_seconds"] = self._frame_seconds()
         return out
 
-    def transcribe_whole(self, path, decode: Callable[[torch.Tensor], str]):
+    def transcribe_whole(self, path, decode: Callable[[torch.Tensor], str], confidences: bool = False):
         """A WAV / FLAC file -> {"text", "words": [{"word", "start", "end"}], "score", "frame_seconds"} from whole(): times in seconds,
         an end cut at the file's own duration, a word a maximal run of labels other than the separator, `decode` the caller's
-        tokenizer.decode (ids tensor -> str).  No confidences (see whole()).  Needs a `mel` and a separator id."""
+        tokenizer.decode (ids tensor -> str).  confidences=True: whole(confidences=True), and every word also carries "confidence" =
+        exp(word_log_confidence), as ASRPipeline.transcribe_timed's do (0 where seg_ok is 0).  Needs a `mel` and a separator id."""
         if self.sep is None:
             raise RuntimeError("LongASRPipeline.transcribe_whole: words need a separator id (whole() gives the label level)")
         wave = self._wave(path, "transcribe_whole")
-        out = self.whole(wave)
+        out = self.whole(wave, confidences=confidences)
         fs = out["frame_seconds"]
         seconds = wave.shape[0] / self.mel.sample_rate
         n = int(out["ids_len"])
@@ -953,6 +974,10 @@ class LongASRPipeline:
             elif first is not None:
                 words.append({"word": decode(ids[first:i]), "start": int(start[first]) * fs, "end": min(int(end[i - 1]) * fs, seconds)})
                 first = None
+        if confidences:                                      # the word level of ctc_segment_long delimits words by the same rule
+            conf = torch.exp(out["word_log_confidence"]).cpu()
+            for w, word in enumerate(words):
+                word["confidence"] = float(conf[w])
         return {"text": decode(ids), "words": words, "score": float(out["score"]), "frame_seconds": fs}
 
 
