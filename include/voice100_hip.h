@@ -945,6 +945,29 @@ int v100_world_stat_parts(int B, int T, int S);
 int v100_world_stat_accum(const float* f0, const int* f0_len, const float* logspc, const float* codeap, double* partial,
                           double* moments, int B, int T, int S, int A, void* stream);
 
+/* ---- K34 n-best rescoring with a word-level back-off n-gram model (csrc/rescore.hip): one launch, no read-back.
+ * ids [B][nbest][T] int64, lens [B][nbest] int32 (clamped to [0, T] on the device), first [B][nbest] fp32: what the beam search
+ * returns; a hypothesis whose first-pass score is -inf (or NaN) is absent.  A word is a maximal run of ids != sep inside the length.
+ * The model, as lm.WordNGramLM.compile() lays it out (voice100_amd/lm.py), on the device: pool [pool_len] int64, the spellings;
+ * wtab [wtab_len] int32, wtab_len / 4 slots (a power of two) of {word id or -1, pool offset, length, 0}; ng [ng_len] int32, per order
+ * n a table of meta[order + n - 1] slots (a power of two) beginning at int32 meta[n - 1], a slot being n word ids (the first -1:
+ * empty), then log p and the back-off weight as fp32 bits.  meta [2 order] int64 is HOST memory.  Word ids: 0 <unk>, 1 <s>, 2 </s>,
+ * then the vocabulary.  has_bos / has_eos: the model lists <s> / </s>; use_eos: add log p(</s> | ...) where it does.
+ * key = first + lm_weight * lm + word_bonus * words in fp64; rank = the number of hypotheses with a greater key, or an equal key and a
+ * lower index; absent ones follow in their order.  Outputs, all [B][nbest] but out_ids [B][nbest][T], by rank r: out_order = the
+ * first-pass index, out_ids / out_lens / out_first = that hypothesis' row, length and first-pass score as given, out_scores = (fp32)
+ * key, out_lm = (fp32) lm, out_nw / out_oov = its words and how many of them are <unk>; -inf, 0, 0, 0 for an absent one.
+ * ws: v100_nbest_rescore_workspace_bytes(B, nbest, T) bytes (-1 = unsupported), need not be zeroed.  No table content and no id can
+ * move an access outside the buffers described here or keep a loop running.
+ * Limits: B >= 1, 1 <= nbest <= 64, 1 <= T <= 4096, 1 <= order <= 8, pool_len, wtab_len, ng_len < 2^31, finite weights; anything else,
+ * or a meta that does not fit ng_len, returns 1; a NULL pointer 3; both before anything touches a device. */
+long long v100_nbest_rescore_workspace_bytes(int B, int nbest, int T);
+int v100_nbest_rescore(const long long* ids, const int* lens, const float* first, const long long* pool, long long pool_len,
+                       const int* wtab, long long wtab_len, const int* ng, long long ng_len, const long long* meta, int order,
+                       int has_bos, int has_eos, void* ws, long long* out_ids, int* out_lens, float* out_scores, float* out_first,
+                       float* out_lm, int* out_nw, int* out_oov, int* out_order, int B, int nbest, int T, long long sep,
+                       double lm_weight, double word_bonus, int use_eos, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,8 @@ nor ctc_align_long (K29): the banded Viterbi that aligns a chapter-length record
 cut a recording of any length, at its pauses, into pieces that the beam search and ctc_segment take, nor CTCBeamStream and
 ctc_beam_search_long (K32): the beam search kept between calls, so that logits can be pushed chunk by chunk and a recording of any
 length is decoded as one utterance, bit for bit what one call over all its frames would give, nor ctc_segment_long and
-ctc_corridor (K33): ctc_segment inside a corridor round a path, for recordings of up to 2^20 frames."""
+ctc_corridor (K33): ctc_segment inside a corridor round a path, for recordings of up to 2^20 frames, nor rescore_nbest (K34): the
+n-best list of the beam search re-ranked by a word-level n-gram model (lm.WordNGramLM), the second pass."""
 import math
 from typing import NamedTuple, Optional
 
@@ -487,6 +488,92 @@ def ctc_beam_search_long(logits: torch.Tensor, lengths: torch.Tensor = None, bea
     for start, frames in beam_chunk_plan(T, chunk):
         stream.push(logits[:, start:start + frames], None if lens is None else beam_chunk_lengths(lens.reshape(-1), start, frames))
     return stream.finish(nbest)
+
+
+class Rescored(NamedTuple):
+    """What rescore_nbest returns, best first after the second pass."""
+    ids: torch.Tensor                                    # [B, nbest, T] int64: the hypotheses' rows as given, re-ordered
+    lens: torch.Tensor                                   # [B, nbest] int32
+    scores: torch.Tensor                                 # [B, nbest] fp32: first + lm_weight * word LM + word_bonus * words; -inf: none
+    first_scores: torch.Tensor                           # [B, nbest] fp32: the first-pass scores as given, re-ordered
+    word_lm_scores: torch.Tensor                         # [B, nbest] fp32: the word model's log probability; 0 where there is no hypothesis
+    n_words: torch.Tensor                                # [B, nbest] int32
+    n_oov: torch.Tensor                                  # [B, nbest] int32: words that are not in the model's vocabulary
+    order: torch.Tensor                                  # [B, nbest] int32: order[b, r] = the first-pass rank of the hypothesis now at rank r
+
+
+def _rescore_launch(ids, lens, scores, word_lm, lm_weight, word_bonus, sep, use_eos, ws=None) -> Rescored:
+    """rescore_nbest's checks and its one launch; ws: a workspace of the caller's (tests), at least
+    v100_nbest_rescore_workspace_bytes(B, nbest, T) bytes."""
+    who = "rescore_nbest"
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (ids, lens, scores)):
+        raise RuntimeError(f"{who}: GPU tensors only")
+    if ids.dim() != 3 or lens.shape != ids.shape[:2] or scores.shape != ids.shape[:2]:
+        raise RuntimeError(f"{who}: ids [B, nbest, T], lens [B, nbest] and scores [B, nbest] as ctc_beam_search returns them, got "
+                           f"{list(ids.shape)}, {list(lens.shape)} and {list(scores.shape)}")
+    tables = (getattr(word_lm, "pool", None), getattr(word_lm, "word_table", None), getattr(word_lm, "ngram_table", None))
+    if any(t is None for t in tables) or getattr(word_lm, "meta", None) is None:
+        raise RuntimeError(f"{who}: the word model is not compiled (WordNGramLM.compile().to(device) first)")
+    dev = ids.device
+    if any(t.device != dev for t in tables):
+        raise RuntimeError(f"{who}: the word model is on {tables[0].device}, the hypotheses on {dev} (word_lm.to(device))")
+    B, nbest, width = ids.shape
+    alpha, beta = float(lm_weight), float(word_bonus)
+    if not (math.isfinite(alpha) and math.isfinite(beta)):
+        raise RuntimeError(f"{who}: lm_weight = {alpha} and word_bonus = {beta} must be finite")
+    ids = ids.to(torch.int64).contiguous()
+    lens, scores = lens.to(torch.int32).contiguous(), scores.float().contiguous()
+    if width == 0:                                       # no column: every hypothesis is empty
+        ids, lens = ids.new_zeros((B, nbest, 1)), torch.zeros_like(lens)
+    T = ids.shape[2]
+    nbytes = N.helper("v100_nbest_rescore_workspace_bytes", B, nbest, T)
+    order = int(word_lm.order)
+    pool, wtab, ng = (t.contiguous() for t in tables)
+    meta = word_lm.meta
+    if (nbytes <= 0 or not 1 <= order <= 8 or pool.dtype != torch.int64 or wtab.dtype != torch.int32 or ng.dtype != torch.int32
+            or meta.dtype != "int64" or meta.size != 2 * order or not meta.flags["C_CONTIGUOUS"]
+            or max(pool.numel(), wtab.numel(), ng.numel()) >= 1 << 31 or not 0 <= int(word_lm.pool_len) <= pool.numel()):
+        raise RuntimeError(f"{who}: unsupported shape or model (B = {B} >= 1, 1 <= nbest = {nbest} <= 64, hypotheses of T = {width} <= 4096 "
+                           f"labels, 1 <= order = {order} <= 8 and tables of fewer than 2^31 elements are the limits)")
+    if ws is None:
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    elif not ws.is_cuda or ws.dtype != torch.uint8 or ws.numel() < nbytes:
+        raise RuntimeError(f"{who}: the workspace must be a uint8 GPU tensor of at least {nbytes} bytes")
+    i32 = lambda: torch.empty((B, nbest), dtype=torch.int32, device=dev)      # noqa: E731
+    f32 = lambda: torch.empty((B, nbest), dtype=torch.float32, device=dev)    # noqa: E731
+    out_ids, out_lens, out_scores, out_first, out_lm, n_words, n_oov, rank = torch.empty_like(ids), i32(), f32(), f32(), f32(), i32(), i32(), i32()
+    try:
+        N.call("v100_nbest_rescore", ids, lens, scores, pool, int(word_lm.pool_len), wtab, wtab.numel(), ng, ng.numel(), meta.ctypes.data,
+               order, int(bool(word_lm.has_bos)), int(bool(word_lm.has_eos)), ws, out_ids, out_lens, out_scores, out_first, out_lm, n_words,
+               n_oov, rank, B, nbest, T, int(sep), alpha, beta, int(bool(use_eos)))
+    except RuntimeError as e:
+        if "status 1" not in str(e):
+            raise
+        raise RuntimeError(f"{who}: the word model's tables do not fit their sizes (meta {meta.tolist()}, word table of {wtab.numel()} "
+                           f"and n-gram table of {ng.numel()} int32: capacities must be powers of two inside the tables)") from None
+    if width == 0:
+        out_ids = out_ids[:, :, :0]
+    return Rescored(out_ids, out_lens, out_scores, out_first, out_lm, n_words, n_oov, rank)
+
+
+def rescore_nbest(ids: torch.Tensor, lens: torch.Tensor, scores: torch.Tensor, word_lm, lm_weight: float = 0.5, word_bonus: float = 0.0,
+                  sep: int = 1, use_eos: bool = True) -> Rescored:
+    """The second pass over an n-best list in one launch (K34, csrc/rescore.hip): ids [B, nbest, T] int64, lens [B, nbest] int32 and
+    scores [B, nbest] fp32 exactly as ctc_beam_search returns them (its first three outputs; with a fused character LM `scores` is the
+    fused score -- pass ctc_scores instead to rank on the acoustic score alone: the caller decides what the first pass is), word_lm
+    a compiled lm.WordNGramLM on the same device -> Rescored, best first.  No read-back inside the call.
+
+    A word is a maximal run of ids != sep inside a hypothesis' length (edit_distance's rule); a word outside the model's vocabulary
+    is <unk>.  Every hypothesis gets word_lm_scores = sum over its words of log p(word | the order - 1 words before it, <s> in front
+    where the model lists it), plus log p(</s> | ...) with use_eos where the model lists </s>, summed in fp64 over the tables' fp32
+    values, and is ranked by scores = first + lm_weight * word_lm_scores + word_bonus * n_words (fp64, stored as fp32): a greater one
+    is ahead, equal ones keep their first-pass order.  A hypothesis that the first pass does not have (score -inf, length 0) stays
+    behind all the others with score -inf, word_lm_scores 0 and no words.  Dtypes and padding are ctc_beam_search's: ids are the given
+    rows, moved whole.  lens are clamped to [0, T] on the device and nothing beyond a hypothesis' length is read; ids may be any
+    int64 (they are hashed and compared, never used as an index).  Two calls give equal bits.
+    Limits: 1 <= nbest <= 64, hypotheses of 0 to 4096 labels (T <= 4096, so up to 2048 words), model order <= 8, tables of fewer
+    than 2^31 elements."""
+    return _rescore_launch(ids, lens, scores, word_lm, lm_weight, word_bonus, sep, use_eos)
 
 
 class CTCSegments(NamedTuple):

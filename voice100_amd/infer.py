@@ -262,14 +262,24 @@ class ASRPipeline:
     hypothesis in the same form, so transcribe, score and evaluate work unchanged, and nbest() returns the `nbest` best with scores.
     lm=<a compiled lm.NGramLM on the model's device> fuses it into that search (K25): hypotheses are ranked by
     log p_ctc + lm_weight * log p_lm + length_bonus * length, and nbest() returns (ids, lens, scores, ctc_scores, lm_scores).
+    word_lm=<a compiled lm.WordNGramLM on the model's device> adds the second pass (K34, decode.rescore_nbest): the search returns its
+    rescore_size best (default: beam_size), they are re-ranked by score + word_lm_weight * log p_word_lm + word_bonus * words (score:
+    the search's own, the fused one with lm=), the call and everything built on it take the top hypothesis after that, and nbest()
+    returns decode.Rescored, cut to `nbest` ranks.  It needs a beam_size; without it every path is what it was.
 
     With `lengths` the rows are utterances of their own lengths: samples per row when the pipeline has a `mel` (the features
     and their frame counts then come from one ragged launch, mel.transform(wav, lengths)), frames per row when it has none
     (wav_or_mel is the padded feature batch); the decode stops at model.output_length(frames) of each row."""
 
-    def __init__(self, model, mel=None, beam_size=None, nbest=1, lm=None, lm_weight=0.5, length_bonus=0.0, frame_seconds=None):
-        if lm is not None and beam_size is None:
+    def __init__(self, model, mel=None, beam_size=None, nbest=1, lm=None, lm_weight=0.5, length_bonus=0.0, frame_seconds=None,
+                 word_lm=None, word_lm_weight=0.5, word_bonus=0.0, rescore_size=None, sep=1):
+        if (lm is not None or word_lm is not None) and beam_size is None:
             raise RuntimeError("ASRPipeline: a language model needs a beam_size (the greedy decode has nothing to rank)")
+        if word_lm is not None:
+            rescore_size = int(beam_size if rescore_size is None else rescore_size)
+            if not 1 <= rescore_size <= beam_size or rescore_size < nbest:
+                raise RuntimeError(f"ASRPipeline: nbest = {nbest} <= rescore_size = {rescore_size} <= beam_size = {beam_size} is required")
+        self.word_lm, self.word_lm_weight, self.word_bonus, self.rescore_size, self.sep = word_lm, word_lm_weight, word_bonus, rescore_size, sep
         self.model, self.mel = model, mel
         self.frame_seconds = frame_seconds                     # seconds per output frame (segments, transcribe_timed); None: from the mel
         self.beam_size, self.nbest_size = beam_size, nbest     # beam_size=None: the greedy decode
@@ -281,6 +291,19 @@ class ASRPipeline:
             return ctc_beam_search(logits, out_len, self.beam_size, nbest)
         return ctc_beam_search(logits, out_len, self.beam_size, nbest, lm=self.lm, lm_weight=self.lm_weight,
                                length_bonus=self.length_bonus)
+
+    def _rescore(self, hyps):
+        """decode.rescore_nbest of a beam search's tuple with the pipeline's word model."""
+        from .decode import rescore_nbest
+        return rescore_nbest(hyps[0], hyps[1], hyps[2], self.word_lm, self.word_lm_weight, self.word_bonus, self.sep)
+
+    def _top(self, logits, out_len):
+        """(ids [B, T'], lens [B], score [B]) of the best hypothesis: the beam search's, or with a word model the second pass'."""
+        if self.word_lm is None:
+            ids, n, score = self._beam(logits, out_len, 1)[:3]
+        else:
+            ids, n, score = self._rescore(self._beam(logits, out_len, self.rescore_size))[:3]
+        return ids[:, 0], n[:, 0], score[:, 0]
 
     def _logits(self, wav_or_mel: torch.Tensor, lengths=None):
         """The model's logits and, with `lengths`, the output frames of each row (else None)."""
@@ -305,18 +328,21 @@ class ASRPipeline:
         from .decode import ctc_greedy_decode
         if self.beam_size is None:
             return ctc_greedy_decode(logits) if out_len is None else ctc_greedy_decode(logits, out_len)
-        ids, n = self._beam(logits, out_len, 1)[:2]
-        return ids[:, 0], n[:, 0]
+        return self._top(logits, out_len)[:2]
 
     @torch.no_grad()
     def nbest(self, wav_or_mel: torch.Tensor, lengths=None):
         """The nbest hypotheses of the beam search, best first: (ids [B, nbest, T'] int64 zero padded, lens [B, nbest] int32,
         scores [B, nbest] fp32 = total log probability; -inf with length 0 where there are fewer hypotheses), and with a language model
-        also ctc_scores and lm_scores [B, nbest] fp32 (scores is then the fused score).  Needs a beam_size."""
+        also ctc_scores and lm_scores [B, nbest] fp32 (scores is then the fused score).  With a word model: decode.Rescored, the
+        `nbest` best of the rescore_size hypotheses after the second pass.  Needs a beam_size."""
         if self.beam_size is None:
             raise RuntimeError("ASRPipeline.nbest: the pipeline was built without a beam_size (the greedy decode has one hypothesis)")
         logits, out_len = self._logits(wav_or_mel, lengths)
-        return self._beam(logits, out_len, self.nbest_size)
+        if self.word_lm is None:
+            return self._beam(logits, out_len, self.nbest_size)
+        from .decode import Rescored
+        return Rescored(*(t[:, :self.nbest_size] for t in self._rescore(self._beam(logits, out_len, self.rescore_size))))
 
     def transcribe(self, paths, decode: Callable[[torch.Tensor], str]) -> List[str]:
         """WAV or FLAC files -> their transcripts: audio_io.load_batch, the ragged pipeline, then `decode` (the caller's tokenizer.decode,
@@ -757,13 +783,15 @@ class LongASRPipeline:
     Device-to-host copies: the number of segments S, one copy of the calls' widths, and the longest hypothesis of each call."""
 
     def __init__(self, model, mel=None, beam_size=None, lm=None, lm_weight=0.5, length_bonus=0.0, keep=1500, max_frames=3000, min_gap=25,
-                 margin=0.0, pad=5, min_frames=50, max_batch=32, blank=0, sep=1, frame_seconds=None, band=2048, seg_band=256):
+                 margin=0.0, pad=5, min_frames=50, max_batch=32, blank=0, sep=1, frame_seconds=None, band=2048, seg_band=256,
+                 word_lm=None, word_lm_weight=0.5, word_bonus=0.0, rescore_size=None):
         if int(blank) != 0:
             raise RuntimeError(f"LongASRPipeline: blank = {blank}; the decode of ASRPipeline takes the blank at id 0")
         if int(max_batch) < 1:
             raise RuntimeError(f"LongASRPipeline: max_batch = {max_batch} must be at least 1")
         self.asr = ASRPipeline(model, mel, beam_size=beam_size, nbest=1, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
-                               frame_seconds=frame_seconds)
+                               frame_seconds=frame_seconds, word_lm=word_lm, word_lm_weight=word_lm_weight, word_bonus=word_bonus,
+                               rescore_size=rescore_size, sep=sep)
         self.model, self.mel = model, mel
         self.keep, self.max_batch, self.blank, self.sep = int(keep), int(max_batch), int(blank), sep
         self.band = int(band)                                # whole(): ctc_align_long's band
@@ -825,8 +853,8 @@ class LongASRPipeline:
                 ids, n = self.asr._best(x, ln)
                 score = None
             else:
-                ids, n, score = self.asr._beam(x, ln, 1)[:3]
-                ids, n, score = ids[:, 0], n[:, 0].contiguous(), score[:, 0]
+                ids, n, score = self.asr._top(x, ln)
+                n = n.contiguous()
             L = max(int(n.max()), 1)
             ids = ids[:, :L].contiguous()
             seg = ctc_segment(x, ln, ids, n, blank=self.blank, sep=self.sep) if with_seg else None
@@ -914,7 +942,9 @@ class LongASRPipeline:
         "word_start", "word_end", "word_log_confidence" and "n_words" (None without a separator id), and "seg_ok" (0-dim int32; 0:
         no alignment inside the corridor, or the aligner lost the path: then the new keys hold what a row without an alignment gets,
         log_prob -inf, times and durations 0, confidences -inf).  The other keys are what they are without it, bit for bit.
-        One read-back, of ids_len, sizes L."""
+        One read-back, of ids_len, sizes L.  With a word model (K34) the search returns its rescore_size best, decode.rescore_nbest re-ranks
+        them (one more read-back, of the longest hypothesis), every key above describes the top one after that, and "first_score" and
+        "word_lm_score" (0-dim) are added."""
         from .decode import ctc_align_long, ctc_beam_search_long, ctc_segment_long
         a = self.asr
         if a.beam_size is None:
@@ -929,13 +959,25 @@ class LongASRPipeline:
         if logits.dim() != 2:
             raise RuntimeError(f"LongASRPipeline.whole: logits must be [T', V], got {list(logits.shape)}")
         logits = logits.contiguous().float()
-        res = ctc_beam_search_long(logits[None], None, a.beam_size, 1, self.blank, a.lm, a.lm_weight, a.length_bonus, chunk=chunk)
+        res = ctc_beam_search_long(logits[None], None, a.beam_size, 1 if a.word_lm is None else a.rescore_size, self.blank, a.lm,
+                                   a.lm_weight, a.length_bonus, chunk=chunk)
+        extra = {}
+        if a.word_lm is not None:                            # the second pass (K34): the top of the rescore_size best, re-ranked
+            width = max(int(res[1].max()), 1)                # a second read-back: the rows are as wide as the frames, the labels far fewer
+            if width > 4096:
+                raise RuntimeError(f"LongASRPipeline.whole: the word model rescores hypotheses of up to 4096 labels, and one has {width} "
+                                   "(segments() rescores piece by piece)")
+            rs = a._rescore((res[0][:, :, :width].contiguous(),) + tuple(res[1:]))
+            top = rs.order[0, 0].long()
+            extra = {"first_score": rs.first_scores[0, 0], "word_lm_score": rs.word_lm_scores[0, 0]}
+            res = (rs.ids, rs.lens, rs.scores) + tuple(t[:, top][:, None] for t in res[3:])
         n = res[1][0, 0]
         L = max(int(n), 1)                                   # the one read-back
         ids = res[0][0, 0, :L].contiguous()
         out = {"ids": ids, "ids_len": n, "score": res[2][0, 0]}
         if a.lm is not None:
             out.update({"ctc_score": res[3][0, 0], "lm_score": res[4][0, 0]})
+        out.update(extra)
         if timed:
             al = ctc_align_long(torch.log_softmax(logits, dim=-1)[None], ids[None], None, n.reshape(1), band=self.band, blank=self.blank)
             ends = torch.cumsum(al.align[0], 0, dtype=torch.int32)[1:2 * L:2]        # label i sits at extended position 2 i + 1
