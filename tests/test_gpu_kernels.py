@@ -1,6 +1,7 @@
 """Kernel-level parity (GPU): each C-ABI entry point against the CPU oracle / torch fp32 on
 seeded inputs.  Tolerance: <= 1e-4 relative (max-abs error / max-abs reference), fp32 paths;
-bf16 GEMM operands: <= 2e-2."""
+bf16 GEMM operands: <= 2e-2.  The per-element float64 checks of the fp32-storage depthwise and 1x1 kernels, in every launch regime,
+are tests/test_gpu_dw_f32_oracle.py and tests/test_gpu_pw_f32_oracle.py."""
 import numpy as np
 import pytest
 import torch
