@@ -968,6 +968,32 @@ int v100_nbest_rescore(const long long* ids, const int* lens, const float* first
                        float* out_lm, int* out_nw, int* out_oov, int* out_order, int B, int nbest, int T, long long sep,
                        double lm_weight, double word_bonus, int use_eos, void* stream);
 
+/* ---- K35 minimum-Bayes-risk selection over an n-best list, and the list's distances to a reference (csrc/mbr.hip): three launches
+ * on `stream` (tokenise once per utterance, one wave per pair, finalise), no read-back.
+ * ids [B][nbest][T] int64, lens [B][nbest] int32 (clamped to [0, T] on the device), scores [B][nbest] fp32: what the beam search or
+ * K34 returns; a hypothesis whose score is -inf (or NaN) is absent, one of length 0 with a finite score is present and empty.
+ * ref [B][Tr] int64 and ref_len [B] int32 (clamped to [0, Tr]): the reference rows, or both NULL and Tr = 0: no reference (ref_dist
+ * and ref_n may then be NULL too and are not written).
+ * A token is one id (words = 0), or a maximal run of ids != sep inside the row's length (words != 0); two words are equal iff their
+ * lengths and ids are (K23's rule; the hash only finds candidates).
+ * In the GIVEN order: dist [B][nbest][nbest] int32 = the Levenshtein distance (unit costs) between the token sequences of hypotheses i
+ * and j, symmetric, 0 on the diagonal, -1 where either is absent; ref_dist [B][nbest] = the distance to the reference, -1 for an absent
+ * hypothesis; ref_n [B] = the reference's tokens; expected_len [B] fp32 = sum_j p_j tokens_j.
+ * p_i = exp(scale (s_i - s_max)) / sum over the present j, fp64 from the fp32 scores, summed in index order, 0 for an absent one;
+ * risk_i = sum_j p_j dist[i][j], an fp64 sum in the order j = 0 .. nbest - 1, stored as fp32, +inf for an absent one.
+ * rank = the number of hypotheses with a smaller STORED fp32 risk, or an equal one and a lower index; absent ones follow in their
+ * order.  By rank r, all [B][nbest] but out_ids [B][nbest][T]: out_order = the given index, out_ids / out_lens / out_scores = that
+ * hypothesis' row (moved whole), length and score as given, out_risk, out_post (fp32 p), out_ntok = its tokens (0 for an absent one).
+ * ws: v100_nbest_mbr_workspace_bytes(B, nbest, T, Tr) bytes (-1 = unsupported), need not be zeroed: the kernels initialise what they
+ * read.  No id and nothing in the workspace can move an access outside the buffers described here or keep a loop running.
+ * Limits: B >= 1, 1 <= nbest <= 64, 1 <= T <= 4096, 1 <= Tr <= 4096 with a reference and Tr = 0 without, finite scale >= 0; anything
+ * else returns 1; a NULL required pointer (or only one of ref / ref_len) 3; both before anything touches a device. */
+long long v100_nbest_mbr_workspace_bytes(int B, int nbest, int T, int Tr);
+int v100_nbest_mbr(const long long* ids, const int* lens, const float* scores, const long long* ref, const int* ref_len, void* ws,
+                   long long* out_ids, int* out_lens, float* out_scores, float* out_risk, float* out_post, int* out_ntok,
+                   int* out_order, int* dist, int* ref_dist, int* ref_n, float* expected_len, int B, int nbest, int T, int Tr,
+                   int words, long long sep, double scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

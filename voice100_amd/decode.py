@@ -576,6 +576,98 @@ def rescore_nbest(ids: torch.Tensor, lens: torch.Tensor, scores: torch.Tensor, w
     return _rescore_launch(ids, lens, scores, word_lm, lm_weight, word_bonus, sep, use_eos)
 
 
+class MBR(NamedTuple):
+    """What mbr_nbest returns: the list by rank (least expected error first), the pairwise distances in the given order."""
+    ids: torch.Tensor                                    # [B, nbest, T] int64: the hypotheses' rows as given, re-ordered
+    lens: torch.Tensor                                   # [B, nbest] int32
+    scores: torch.Tensor                                 # [B, nbest] fp32: the scores as given, re-ordered
+    risk: torch.Tensor                                   # [B, nbest] fp32: the expected number of token errors; +inf: no hypothesis
+    posterior: torch.Tensor                              # [B, nbest] fp32: the list's posterior; 0: no hypothesis
+    n_tokens: torch.Tensor                               # [B, nbest] int32: words (or ids with sep=None)
+    order: torch.Tensor                                  # [B, nbest] int32: order[b, r] = the given index of the hypothesis now at rank r
+    dist: torch.Tensor                                   # [B, nbest, nbest] int32, GIVEN order: pairwise distances; -1: one is absent
+    expected_len: torch.Tensor                           # [B] fp32: the posterior mean of the token count
+    ref_dist: Optional[torch.Tensor]                     # [B, nbest] int32, GIVEN order: distances to the reference; None without one
+    ref_n: Optional[torch.Tensor]                        # [B] int32: the reference's tokens; None without one
+
+
+def _mbr_launch(ids, lens, scores, sep, scale, ref, ref_len, ws=None) -> MBR:
+    """mbr_nbest's checks and its three launches; ws: a workspace of the caller's (tests), at least
+    v100_nbest_mbr_workspace_bytes(B, nbest, T, Tr) bytes."""
+    who = "mbr_nbest"
+    given = (ids, lens, scores) + (() if ref is None and ref_len is None else (ref, ref_len))
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in given):
+        raise RuntimeError(f"{who}: GPU tensors only")
+    if ids.dim() != 3 or lens.shape != ids.shape[:2] or scores.shape != ids.shape[:2]:
+        raise RuntimeError(f"{who}: ids [B, nbest, T], lens [B, nbest] and scores [B, nbest] as ctc_beam_search returns them, got "
+                           f"{list(ids.shape)}, {list(lens.shape)} and {list(scores.shape)}")
+    dev = ids.device
+    B, nbest, width = ids.shape
+    has_ref = ref is not None
+    if has_ref and (ref.dim() != 2 or ref.shape[0] != B or ref_len.numel() != B):
+        raise RuntimeError(f"{who}: ref [B, Tr] and ref_len [B] with B = {B}, got {list(ref.shape)} and {list(ref_len.shape)}")
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale >= 0.0):
+        raise RuntimeError(f"{who}: scale = {scale} must be finite and not negative")
+    ids = ids.to(torch.int64).contiguous()
+    lens, scores = lens.to(torch.int32).contiguous(), scores.float().contiguous()
+    if width == 0:                                       # no column: every hypothesis is empty
+        ids, lens = ids.new_zeros((B, nbest, 1)), torch.zeros_like(lens)
+    T, Tr, rl = ids.shape[2], 0, None
+    if has_ref:
+        ref = ref.to(device=dev, dtype=torch.int64).contiguous()
+        rl = ref_len.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        if ref.shape[1] == 0:
+            ref, rl = ref.new_zeros((B, 1)), torch.zeros_like(rl)
+        Tr = ref.shape[1]
+    nbytes = N.helper("v100_nbest_mbr_workspace_bytes", B, nbest, T, Tr) if B >= 1 else -1
+    if nbytes <= 0:
+        raise RuntimeError(f"{who}: unsupported shape (B = {B} >= 1, 1 <= nbest = {nbest} <= 64, hypotheses of T = {width} <= 4096 labels "
+                           f"and a reference of Tr = {Tr} <= 4096 labels are the limits)")
+    if ws is None:
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    elif not ws.is_cuda or ws.dtype != torch.uint8 or ws.numel() < nbytes:
+        raise RuntimeError(f"{who}: the workspace must be a uint8 GPU tensor of at least {nbytes} bytes")
+    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)          # noqa: E731
+    f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)        # noqa: E731
+    out_ids, out_lens, out_scores, risk, post, ntok, order = torch.empty_like(ids), i32(B, nbest), f32(B, nbest), f32(B, nbest), \
+        f32(B, nbest), i32(B, nbest), i32(B, nbest)
+    dist, elen = i32(B, nbest, nbest), f32(B)
+    ref_dist, ref_n = (i32(B, nbest), i32(B)) if has_ref else (None, None)
+    N.call("v100_nbest_mbr", ids, lens, scores, ref if has_ref else None, rl, ws, out_ids, out_lens, out_scores, risk, post, ntok, order,
+           dist, ref_dist, ref_n, elen, B, nbest, T, Tr, 0 if sep is None else 1, 0 if sep is None else int(sep), scale)
+    if width == 0:
+        out_ids = out_ids[:, :, :0]
+    return MBR(out_ids, out_lens, out_scores, risk, post, ntok, order, dist, elen, ref_dist, ref_n)
+
+
+def mbr_nbest(ids: torch.Tensor, lens: torch.Tensor, scores: torch.Tensor, sep=1, scale: float = 1.0, ref: torch.Tensor = None,
+              ref_len: torch.Tensor = None) -> MBR:
+    """Minimum-Bayes-risk selection over an n-best list (K35, csrc/mbr.hip; three launches, no read-back): ids [B, nbest, T] int64,
+    lens [B, nbest] int32 and scores [B, nbest] fp32 exactly as ctc_beam_search or rescore_nbest return them -> MBR, the hypothesis
+    with the least expected number of token errors under the list's posterior first.
+
+    A hypothesis is absent when its score is -inf or NaN; one of length 0 with a finite score is present and empty.  sep=<id>: a token
+    is a word, a maximal run of ids != sep inside the hypothesis' length, and two words are equal iff they have the same length and
+    the same ids; sep=None: a token is one id (edit_distance's convention at both levels).
+      dist[b, i, j]    the Levenshtein distance (unit costs) between the token sequences of hypotheses i and j, in the GIVEN order:
+                       symmetric, 0 on the diagonal, -1 where either is absent;
+      posterior[b, i]  exp(scale (s_i - s_max)) / the sum over the present hypotheses, in fp64 from the fp32 scores; 0 for an absent one;
+      risk[b, i]       sum_j posterior_j dist[i, j] (fp64, stored as fp32): the expected number of token errors of i; +inf for an absent one;
+      expected_len[b]  sum_j posterior_j n_tokens_j, so risk / expected_len is the expected error rate: a quality estimate per utterance
+                       that needs no reference;
+      order            by the stored fp32 risk, smaller first; equal risks keep the given order; absent hypotheses follow in the given
+                       order.  ids (rows moved whole), lens, scores, risk, posterior and n_tokens are in that order.
+    ref [B, Tr] int64 with ref_len [B]: ref_dist[b, i] = the distance of hypothesis i (GIVEN order) to the reference, -1 for an absent
+    one, and ref_n[b] = the reference's tokens -- the list's oracle error is ref_dist's minimum over the present ones.
+
+    What the numbers are not: the posterior is over the LIST, not over all transcripts, so risk underestimates the true expected error
+    when the list is short, and scale is not calibrated here (1.0 takes the scores as log probabilities).
+    lens and ref_len are clamped to [0, width] on the device and nothing beyond a row's length is read; ids may be any int64 (hashed
+    and compared, never an index).  Two calls give equal bits.  Limits: 1 <= nbest <= 64, T and Tr <= 4096, finite scale >= 0."""
+    return _mbr_launch(ids, lens, scores, sep, scale, ref, ref_len)
+
+
 class CTCSegments(NamedTuple):
     """What ctc_segment returns; the word fields are None with sep=None."""
     log_prob: torch.Tensor                               # [B] fp32: log p(labels | logits), summed over all alignments

@@ -13,6 +13,7 @@ Reference call sites this serves:
 Nothing here computes on the CPU: the pipelines call the HIP-backed modules; `scatter_run` is plumbing over
 torch.distributed ("nccl" = RCCL on the GPU box, "gloo" in the CPU tests, where a stock-op stand-in model is used).
 """
+import math
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
@@ -266,20 +267,38 @@ class ASRPipeline:
     rescore_size best (default: beam_size), they are re-ranked by score + word_lm_weight * log p_word_lm + word_bonus * words (score:
     the search's own, the fused one with lm=), the call and everything built on it take the top hypothesis after that, and nbest()
     returns decode.Rescored, cut to `nbest` ranks.  It needs a beam_size; without it every path is what it was.
+    mbr="word" or "id" adds minimum-Bayes-risk selection (K35, decode.mbr_nbest) as the last stage: the search returns its mbr_size best
+    (default: rescore_size with a word model, else beam_size; with a word model the second pass re-ranks that same list), and the call
+    and everything built on it take the hypothesis with the least expected number of word (sep) or id errors under the posterior
+    exp(mbr_scale * score) of the last stage's scores, which is not always the one with the best score.  nbest() returns decode.MBR,
+    its rank-ordered fields cut to `nbest` ranks (dist, in the given order, and expected_len stay whole).  It needs a beam_size;
+    with mbr=None every path executes exactly the calls it executes without the argument.
 
     With `lengths` the rows are utterances of their own lengths: samples per row when the pipeline has a `mel` (the features
     and their frame counts then come from one ragged launch, mel.transform(wav, lengths)), frames per row when it has none
     (wav_or_mel is the padded feature batch); the decode stops at model.output_length(frames) of each row."""
 
     def __init__(self, model, mel=None, beam_size=None, nbest=1, lm=None, lm_weight=0.5, length_bonus=0.0, frame_seconds=None,
-                 word_lm=None, word_lm_weight=0.5, word_bonus=0.0, rescore_size=None, sep=1):
+                 word_lm=None, word_lm_weight=0.5, word_bonus=0.0, rescore_size=None, sep=1, mbr=None, mbr_scale=1.0, mbr_size=None):
         if (lm is not None or word_lm is not None) and beam_size is None:
             raise RuntimeError("ASRPipeline: a language model needs a beam_size (the greedy decode has nothing to rank)")
+        if mbr is not None:
+            if mbr not in ("word", "id"):
+                raise RuntimeError(f"ASRPipeline: mbr = {mbr!r} must be None, \"word\" or \"id\"")
+            if beam_size is None:
+                raise RuntimeError("ASRPipeline: mbr needs a beam_size (the greedy decode has one hypothesis)")
+            if not (math.isfinite(float(mbr_scale)) and float(mbr_scale) >= 0.0):
+                raise RuntimeError(f"ASRPipeline: mbr_scale = {mbr_scale} must be finite and not negative")
         if word_lm is not None:
             rescore_size = int(beam_size if rescore_size is None else rescore_size)
             if not 1 <= rescore_size <= beam_size or rescore_size < nbest:
                 raise RuntimeError(f"ASRPipeline: nbest = {nbest} <= rescore_size = {rescore_size} <= beam_size = {beam_size} is required")
         self.word_lm, self.word_lm_weight, self.word_bonus, self.rescore_size, self.sep = word_lm, word_lm_weight, word_bonus, rescore_size, sep
+        if mbr is not None:
+            mbr_size = int((rescore_size if word_lm is not None else beam_size) if mbr_size is None else mbr_size)
+            if not nbest <= mbr_size <= beam_size or mbr_size < 1:
+                raise RuntimeError(f"ASRPipeline: nbest = {nbest} <= mbr_size = {mbr_size} <= beam_size = {beam_size} is required")
+        self.mbr, self.mbr_scale, self.mbr_size = mbr, float(mbr_scale), mbr_size
         self.model, self.mel = model, mel
         self.frame_seconds = frame_seconds                     # seconds per output frame (segments, transcribe_timed); None: from the mel
         self.beam_size, self.nbest_size = beam_size, nbest     # beam_size=None: the greedy decode
@@ -297,9 +316,22 @@ class ASRPipeline:
         from .decode import rescore_nbest
         return rescore_nbest(hyps[0], hyps[1], hyps[2], self.word_lm, self.word_lm_weight, self.word_bonus, self.sep)
 
+    def _mbr(self, hyps):
+        """decode.mbr_nbest of the first three tensors of a beam search's or a second pass' tuple, at the pipeline's level and scale."""
+        from .decode import mbr_nbest
+        return mbr_nbest(hyps[0], hyps[1], hyps[2], sep=self.sep if self.mbr == "word" else None, scale=self.mbr_scale)
+
+    def _mbr_list(self, logits, out_len):
+        """beam -> (word rescoring, if configured, over the same list) -> mbr_nbest on the scores of the last stage."""
+        hyps = self._beam(logits, out_len, self.mbr_size)
+        return self._mbr(hyps if self.word_lm is None else self._rescore(hyps))
+
     def _top(self, logits, out_len):
-        """(ids [B, T'], lens [B], score [B]) of the best hypothesis: the beam search's, or with a word model the second pass'."""
-        if self.word_lm is None:
+        """(ids [B, T'], lens [B], score [B]) of the best hypothesis: the beam search's, with a word model the second pass', with mbr
+        the one of least expected error."""
+        if self.mbr is not None:
+            ids, n, score = self._mbr_list(logits, out_len)[:3]
+        elif self.word_lm is None:
             ids, n, score = self._beam(logits, out_len, 1)[:3]
         else:
             ids, n, score = self._rescore(self._beam(logits, out_len, self.rescore_size))[:3]
@@ -335,10 +367,14 @@ class ASRPipeline:
         """The nbest hypotheses of the beam search, best first: (ids [B, nbest, T'] int64 zero padded, lens [B, nbest] int32,
         scores [B, nbest] fp32 = total log probability; -inf with length 0 where there are fewer hypotheses), and with a language model
         also ctc_scores and lm_scores [B, nbest] fp32 (scores is then the fused score).  With a word model: decode.Rescored, the
-        `nbest` best of the rescore_size hypotheses after the second pass.  Needs a beam_size."""
+        `nbest` best of the rescore_size hypotheses after the second pass.  With mbr: decode.MBR, ids, lens, scores, risk, posterior,
+        n_tokens and order cut to `nbest` ranks; dist (given order, [B, mbr_size, mbr_size]) and expected_len whole.  Needs a beam_size."""
         if self.beam_size is None:
             raise RuntimeError("ASRPipeline.nbest: the pipeline was built without a beam_size (the greedy decode has one hypothesis)")
         logits, out_len = self._logits(wav_or_mel, lengths)
+        if self.mbr is not None:
+            m = self._mbr_list(logits, out_len)
+            return type(m)(*(t[:, :self.nbest_size] for t in m[:7]), *m[7:])
         if self.word_lm is None:
             return self._beam(logits, out_len, self.nbest_size)
         from .decode import Rescored
@@ -784,14 +820,14 @@ class LongASRPipeline:
 
     def __init__(self, model, mel=None, beam_size=None, lm=None, lm_weight=0.5, length_bonus=0.0, keep=1500, max_frames=3000, min_gap=25,
                  margin=0.0, pad=5, min_frames=50, max_batch=32, blank=0, sep=1, frame_seconds=None, band=2048, seg_band=256,
-                 word_lm=None, word_lm_weight=0.5, word_bonus=0.0, rescore_size=None):
+                 word_lm=None, word_lm_weight=0.5, word_bonus=0.0, rescore_size=None, mbr=None, mbr_scale=1.0, mbr_size=None):
         if int(blank) != 0:
             raise RuntimeError(f"LongASRPipeline: blank = {blank}; the decode of ASRPipeline takes the blank at id 0")
         if int(max_batch) < 1:
             raise RuntimeError(f"LongASRPipeline: max_batch = {max_batch} must be at least 1")
         self.asr = ASRPipeline(model, mel, beam_size=beam_size, nbest=1, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
                                frame_seconds=frame_seconds, word_lm=word_lm, word_lm_weight=word_lm_weight, word_bonus=word_bonus,
-                               rescore_size=rescore_size, sep=sep)
+                               rescore_size=rescore_size, sep=sep, mbr=mbr, mbr_scale=mbr_scale, mbr_size=mbr_size)
         self.model, self.mel = model, mel
         self.keep, self.max_batch, self.blank, self.sep = int(keep), int(max_batch), int(blank), sep
         self.band = int(band)                                # whole(): ctc_align_long's band
@@ -944,7 +980,8 @@ class LongASRPipeline:
         log_prob -inf, times and durations 0, confidences -inf).  The other keys are what they are without it, bit for bit.
         One read-back, of ids_len, sizes L.  With a word model (K34) the search returns its rescore_size best, decode.rescore_nbest re-ranks
         them (one more read-back, of the longest hypothesis), every key above describes the top one after that, and "first_score" and
-        "word_lm_score" (0-dim) are added."""
+        "word_lm_score" (0-dim) are added.  With mbr (K35) the search returns its mbr_size best, the second pass (if any) re-ranks them,
+        decode.mbr_nbest picks the one of least expected error, every key describes that one, and "risk" and "expected_len" are added."""
         from .decode import ctc_align_long, ctc_beam_search_long, ctc_segment_long
         a = self.asr
         if a.beam_size is None:
@@ -959,10 +996,24 @@ class LongASRPipeline:
         if logits.dim() != 2:
             raise RuntimeError(f"LongASRPipeline.whole: logits must be [T', V], got {list(logits.shape)}")
         logits = logits.contiguous().float()
-        res = ctc_beam_search_long(logits[None], None, a.beam_size, 1 if a.word_lm is None else a.rescore_size, self.blank, a.lm,
-                                   a.lm_weight, a.length_bonus, chunk=chunk)
+        size = a.mbr_size if a.mbr is not None else 1 if a.word_lm is None else a.rescore_size
+        res = ctc_beam_search_long(logits[None], None, a.beam_size, size, self.blank, a.lm, a.lm_weight, a.length_bonus, chunk=chunk)
         extra = {}
-        if a.word_lm is not None:                            # the second pass (K34): the top of the rescore_size best, re-ranked
+        if a.mbr is not None:                                # K35 as the last stage, after the second pass where there is one
+            width = max(int(res[1].max()), 1)                # a second read-back: the rows are as wide as the frames, the labels far fewer
+            if width > 4096:
+                raise RuntimeError(f"LongASRPipeline.whole: mbr takes hypotheses of up to 4096 labels, and one has {width} "
+                                   "(segments() selects piece by piece)")
+            hyps = (res[0][:, :, :width].contiguous(),) + tuple(res[1:3])
+            rs = None if a.word_lm is None else a._rescore(hyps)
+            m = a._mbr(hyps if rs is None else rs)
+            top = m.order[0, 0].long()                       # its index in the list that mbr_nbest was given
+            extra = {"risk": m.risk[0, 0], "expected_len": m.expected_len[0]}
+            if rs is not None:
+                extra.update({"first_score": rs.first_scores[0, top], "word_lm_score": rs.word_lm_scores[0, top]})
+                top = rs.order[0, top].long()
+            res = (m.ids, m.lens, m.scores) + tuple(t[:, top][:, None] for t in res[3:])
+        elif a.word_lm is not None:                          # the second pass (K34): the top of the rescore_size best, re-ranked
             width = max(int(res[1].max()), 1)                # a second read-back: the rows are as wide as the frames, the labels far fewer
             if width > 4096:
                 raise RuntimeError(f"LongASRPipeline.whole: the word model rescores hypotheses of up to 4096 labels, and one has {width} "
